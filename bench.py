@@ -13,6 +13,12 @@ hooks a real run uses (lsnet_amd/runner).  Inputs are resident in HBM before the
 
 Prints ONE JSON line (rank 0):  value = total images / s over all N GPUs (weak scaling, 2 img/GPU).
   value        : at the library's default arithmetic 'bf16x6' = fp32-equivalent (include/lsnet_hip.h).
+  ms_per_step  : wall-clock milliseconds of one of the K timed steps.
+
+A plain run sets up, runs the W warm-up steps, times the K steps, writes the outputs of the last step when
+--dump-outputs DIR is given, and prints the line with the fields above (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config, loss).  Everything else it can measure or check runs only with --full:
+  loss_iter0   : the untouched model's losses on the bench batch against the reference's (tests/golden/bench_iter0.npz).
   roofline     : the hand-written kernel family with the most GPU time in the step, chosen over ALL instrumented families
                  (deformable conv forward / backward-data / weight gradient, dense conv forward / data gradient / weight
                  gradient, normalisation passes) by a survey pass of 3 untimed steps with HIP events around every launch;
@@ -76,6 +82,13 @@ def parse():
     ap.add_argument('--graph', action='store_true',
                     help='replay forward+backward from one captured hipGraph (runner/graph_step.py) instead of '
                          'launching every kernel eagerly; same speed while the step is GPU-bound')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every other measurement and check: iteration-0 loss parity, the per-family kernel '
+                         'survey and roofline, the all-reduce probes, the other arithmetic modes, inference, configs 3 / 4 '
+                         'and the CPU baseline (the --no-* flags above still switch legs off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed (its losses, a seeded sample of the '
+                         'updated parameters and of their gradients) as DIR/<name>.npy')
     return ap.parse_args()
 
 
@@ -401,6 +414,33 @@ def allreduce_probe(model, dev, world, reps=5):
                 allreduce_algbw_gbps=nbytes / dt / 1e9)
 
 
+DUMP_SAMPLE = 1 << 22   # elements per sampled array: two float32 arrays of 16 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, model, out):
+    """What the timed path hands its caller after the last step: the losses of that step (float64 scalars, one file per
+    entry of log_vars) and its effect on the model -- the trainable parameters after the update and the gradients that
+    produced it, both as the same fixed, seeded sample (DUMP_SAMPLE elements, sorted indices drawn with DUMP_SEED) of
+    the flat vector of all trainable parameters in named_parameters() order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in out['log_vars'].items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), np.asarray(float(v.detach() if torch.is_tensor(v) else v), np.float64))
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_SAMPLE].sort().values
+        idx = idx.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    np.save(os.path.join(out_dir, 'params_sample.npy'), flat_p.float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'grads_sample.npy'), flat_g.float().cpu().numpy())
+    del flat_p, flat_g
+
+
 def main():
     args = parse()
     if args.cpu_baseline_worker:
@@ -435,8 +475,9 @@ def main():
         model = model.to(memory_format=torch.channels_last)
     model.train()
     model = DataParallelModel(model)   # N = 1: the gradient arena alone (no communication), as train_detector builds it
+    full = args.full
     exposed = []   # N > 1: (start, end) events around the wait for the gradient all-reduces = what backward did not hide
-    if world > 1:
+    if world > 1 and full:
         finish = model.reduce_gradients
 
         def timed_finish():
@@ -449,8 +490,8 @@ def main():
     step, runner = build_step(model, cfg)
     data = synthetic_batch(args.task, args.batch, args.height, args.width, seed=1234 + rank, device=dev,
                            channels_last=not args.nchw)
-    iter0 = iteration0_losses(model, data) if rank == 0 else None   # before any update: SURVEY 8(d) "Loss parity"
-    timer = None if args.no_kernel_timing else KernelTimer()
+    iter0 = iteration0_losses(model, data) if rank == 0 and full else None   # before any update: SURVEY 8(d) "Loss parity"
+    timer = KernelTimer() if full and not args.no_kernel_timing else None
     survey, dominant = {}, None
     use_graph = args.graph
     if use_graph:
@@ -495,6 +536,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, out)
     exposed_ms = sum(a.elapsed_time(b) for a, b in exposed) / max(len(exposed), 1) if exposed else 0.0
     ks = timer.stop() if (timer and not use_graph) else {}
     if markers:
@@ -505,6 +548,7 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and full:
         mine = torch.tensor([dt_rank / args.steps * 1e3, exposed_ms], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -520,10 +564,10 @@ def main():
         for _ in range(nk):
             gs._fwd_bwd(data)
         ks = timer.stop()
-    comm = allreduce_probe(model, dev, world) if world > 1 else None
+    comm = allreduce_probe(model, dev, world) if world > 1 and full else None
     flush_c_stdio()   # (the communicators exist by now: RCCL's banner, if any, is out before the JSON line)
     comm1 = None
-    if world == 1 and not args.no_extra:
+    if world == 1 and full and not args.no_extra:
         # the same buckets through a ONE-rank RCCL group: what a stand-alone gradient all-reduce of this step costs on this
         # box before any second GPU is involved (launch + RCCL's own kernels; tests/test_rccl_single_gpu.py runs the
         # hook-driven path the same way).  Reported under config, never part of `value`.
@@ -556,7 +600,7 @@ def main():
             comm1 = {'allreduce_ms_per_step_standalone': None, 'error': f'{type(ex).__name__}: {ex}'}
 
     extra = {}
-    if world == 1 and not use_graph and not args.no_extra:
+    if world == 1 and full and not use_graph and not args.no_extra:
         for mode in ('bf16x3', 'fp32'):
             if mode == args.math:
                 continue
@@ -613,8 +657,9 @@ def main():
                 res['config']['rccl_version'] = '.'.join(str(v) for v in torch.cuda.nccl.version())
             except Exception:
                 res['config']['rccl_version'] = 'unknown'
-            res['config'].update(comm)
             res['config']['rccl_ranks'] = dist.get_world_size()    # what the process group reports, not the flag
+        if world > 1 and full:
+            res['config'].update(comm)
             res['config']['per_rank_ms_per_step'] = [r[0] for r in per_rank]
             # GPU time the compute stream spent waiting for the bucket all-reduces after backward (mean per step, per rank):
             # the part of `allreduce_ms_per_step_standalone` that backward did NOT hide
@@ -678,7 +723,7 @@ def main():
                 res['roofline']['bound_by_counters'] = 'hbm' if cg / HBM_PEAK_GBPS > k['tflops'] / peak else 'mfma'
         if extra:
             res['extra'] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             try:
                 res['cpu_baseline'] = cpu_baseline(args)
             except Exception as ex:   # the baseline must never take the bench line down

@@ -742,13 +742,124 @@ def golden_data_pipeline():
     _save('data_pipeline', data)
 
 
+REF_CFG_DIR = os.path.join(bootstrap.REF_ROOT, 'configs', 'lsnet')
+
+
+def _cfg_plain(d):
+    """A loaded config section as JSON-able data; tuples kept apart from lists ({'__tuple__': [...]}) because the
+    pipeline stages tell them apart (Resize: one scale vs a list of scales).  tests/golden_util.py::load_ref_configs
+    reverses it."""
+    if isinstance(d, dict):
+        return {k: _cfg_plain(v) for k, v in d.items()}
+    if isinstance(d, tuple):
+        return {'__tuple__': [_cfg_plain(v) for v in d]}
+    if isinstance(d, list):
+        return [_cfg_plain(v) for v in d]
+    return d
+
+
+def golden_ref_configs():
+    """configs/lsnet/*.py of the reference, loaded by the reference's own mmcv.Config: the sections tests/test_configs.py
+    compares the model zoo and the data pipelines with (model, train_cfg, test_cfg, optimizer, optimizer_config, data).
+    -> tests/golden/ref_configs.json"""
+    import json
+    import mmcv
+    out = {}
+    for f in sorted(os.listdir(REF_CFG_DIR)):
+        if not f.endswith('.py'):
+            continue
+        cfg = mmcv.Config.fromfile(os.path.join(REF_CFG_DIR, f))
+        out[f] = {k: _cfg_plain(cfg._cfg_dict.to_dict()[k])
+                  for k in ('model', 'train_cfg', 'test_cfg', 'optimizer', 'optimizer_config', 'data')}
+    path = os.path.join(OUT, 'ref_configs.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, sort_keys=True, separators=(',', ':'))
+    print(f'ref_configs: {os.path.getsize(path) / 1024:.1f} KiB, {len(out)} files')
+
+
+def golden_cpv_assigner():
+    """The reference's PointHMAssigner (mmdet/core/bbox/assigners/point_hm_assigner.py) on the cases of
+    tests/test_cpv.py::test_corner_heatmap_assigner_equals_reference, every output in full."""
+    from mmdet.core.bbox.assigners.point_hm_assigner import PointHMAssigner as Ref
+    from lsnet_amd.core import PointGenerator
+    pts = torch.cat([PointGenerator().grid_points((-(-384 // s), -(-512 // s)), s, 'cpu') for s in (8, 16, 32, 64, 128)])
+    data = {}
+    for seed, n in ((1, 5), (2, 9), (3, 1), (4, 30)):
+        b, l, _ = gu.make_gt(seed, n, 384, 512, num_classes=8)
+        for bump in (True, False):
+            for i, x in enumerate(Ref(bump, 0.7).assign(pts, b, l)):
+                data[f'{seed}/{int(bump)}/{i}'] = x.numpy()
+    keep = torch.rand(pts.shape[0], generator=gu.gen(0)) < 0.7
+    for i, x in enumerate(Ref(True, 0.7).assign(pts[keep], b, l)):
+        data[f'keep/{i}'] = x.numpy()
+    _save('cpv_assigner', data)
+
+
+def golden_edge_targets():
+    """The reference's LSHead / LSCPVHead losses on the edge cases of tests/test_cpv.py::test_target_edge_cases_equal_reference
+    (one image without objects; one image smaller than the padded batch), same weights (fill seed 7) and inputs."""
+    import mmcv
+    from mmdet.models import build_head as ref_build
+    data = {}
+    for kind in ('bbox', 'cpv'):
+        for case in ('empty', 'ragged'):
+            cfg, tr, te = gu.cpv_head_cfg() if kind == 'cpv' else gu.head_cfg('bbox')
+            rc = mmcv.Config(copy.deepcopy(cfg))._cfg_dict
+            rc.update(train_cfg=mmcv.Config(tr), test_cfg=mmcv.Config(te))
+            head = gu.fill_params(ref_build(rc), seed=7).train()
+            boxes, labels, ext, metas, sem, wts = gu.edge_case_targets(case)
+            outs = head([f.clone() for f in gu.head_inputs(11)])
+            if kind == 'cpv':
+                losses = head.loss(*outs, boxes, ext, sem, wts, labels, metas)
+            else:
+                losses = head.loss(*outs, gt_bboxes=boxes, gt_extremes=ext, gt_keypoints_vs=None, gt_masks=None,
+                                   gt_labels=labels, img_metas=metas)
+            for k, v in losses.items():
+                data[f'{kind}/{case}/{k}'] = np.array([float(x) for x in (v if isinstance(v, (list, tuple)) else [v])])
+    _save('edge_targets', data)
+
+
+def golden_samplers():
+    """The reference's DistributedGroupSampler / GroupSampler (mmdet/datasets/samplers/) on the toy datasets of
+    tests/test_data_pipeline.py (its _dataset): the index order of every rank and epoch resp. seed, in full."""
+    from mmdet.datasets.samplers import DistributedGroupSampler, GroupSampler
+    from tests.test_data_pipeline import _dataset
+    data = {}
+    for n, spg, world in ((103, 2, 8), (64, 4, 2), (37, 3, 1)):
+        ds = _dataset(n, n)
+        for r in range(world):
+            s = DistributedGroupSampler(ds, spg, world, r)
+            for ep in (0, 5):
+                s.set_epoch(ep)
+                data[f'dist/{n}/{spg}/{world}/{r}/{ep}'] = np.array([int(i) for i in s], np.int64)
+    for n, spg in ((23, 2), (40, 4), (7, 3)):
+        ds = _dataset(n, n)
+        np.random.seed(n)
+        data[f'single/{n}/{spg}'] = np.array([int(i) for i in GroupSampler(ds, spg)], np.int64)
+    _save('samplers', data)
+
+
+def golden_nms_refbuild():
+    """The reference's own nms_cpu.cpp (compiled into oracle/_ref by oracle/build_ref.py) on the cases of
+    tests/test_oracle.py::test_nms_against_reference_build: the kept indices in full."""
+    from oracle import build_ref
+    assert build_ref.build() is not None
+    ref = build_ref.load()
+    data = {}
+    for n, thr, dets in gu.nms_cases():
+        data[f'{n}/{thr}'] = ref.nms(dets, thr).numpy()
+    _save('nms_refbuild', data)
+
+
 ALL = dict(decode=golden_decode, decode_cpv=golden_decode_cpv, backbones_dcn=golden_backbones_dcn, bench_iter0=golden_bench_iter0, train_curve=golden_train_curve,
            # the same run at a tenth of the learning rate: the loss falls 475 -> 60 instead of 475 -> 1 and rounding
            # differences between two correct implementations stay at rounding level over all twelve iterations
            train_curve_lowlr=lambda: golden_train_curve(0.001, 'train_curve_lowlr'), train_curve_init0=lambda: golden_train_curve(0.01, 'train_curve_init0', init0=True), coco_eval=golden_coco_eval, head_cpv=golden_head_cpv, data_pipeline=golden_data_pipeline, gt_formats=golden_gt_formats, res2net=golden_res2net, vote=golden_vote, head_bbox=lambda: golden_head('bbox'), head_segm=lambda: golden_head('segm'),
            head_bbox_256=lambda: golden_head('bbox', 256),
            head_pose_bbox=lambda: golden_head('pose_bbox'), head_pose_kbox=lambda: golden_head('pose_kbox'),
-           assign=golden_assign, cross_iou=golden_cross_iou, backbone=golden_backbone, nms=golden_nms)
+           assign=golden_assign, cross_iou=golden_cross_iou, backbone=golden_backbone, nms=golden_nms,
+           ref_configs=golden_ref_configs, cpv_assigner=golden_cpv_assigner, edge_targets=golden_edge_targets,
+           samplers=golden_samplers, nms_refbuild=golden_nms_refbuild)
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()

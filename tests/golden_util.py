@@ -2,6 +2,7 @@
 (oracle/ref_harness/make_golden.py, runs against the reference in the build container) and by the
 parity tests (which run wherever the fixtures under tests/golden/ are).  Pure torch/numpy on CPU:
 the same code yields bit-identical inputs on both sides."""
+import os
 import types
 import zlib
 
@@ -444,3 +445,55 @@ def backbone_grad_names(bb):
 
 
 CURVE0_HW = (384, 512)   # training-curve fixture of the seed-0 init_weights model: 2 images of this size per iteration
+
+
+def edge_case_targets(case):
+    """Targets of tests/test_cpv.py::test_target_edge_cases_equal_reference at HEAD_IMG: 'empty' = the second image has no
+    objects; 'ragged' = the second image is 384 x 400 inside the padded batch.  -> boxes, labels, extremes, metas, semantic
+    maps, their weights."""
+    h, w = HEAD_IMG
+    b0, l0, e0 = make_gt(100, 4, h, w, num_classes=8)
+    if case == 'empty':
+        boxes, labels, ext = [b0, b0[:0]], [l0, l0[:0]], [e0, e0[:0]]
+        small = (h, w)
+    else:
+        small = (384, 400)                                 # >= 9 cells on the coarsest level, as ATSS needs
+        b1, l1, e1 = make_gt(101, 3, *small, num_classes=8)
+        boxes, labels, ext = [b0, b1], [l0, l1], [e0, e1]
+    metas = [dict(pad_shape=(h, w, 3), img_shape=(h, w, 3), scale_factor=1.0),
+             dict(pad_shape=small + (3,), img_shape=small + (3,), scale_factor=1.0)]
+    sem, wts = make_sem_maps(boxes, labels, h, w, 8)
+    return boxes, labels, ext, metas, sem, wts
+
+
+def _cfg_from_json(d):
+    if isinstance(d, dict):
+        if set(d) == {'__tuple__'}:
+            return tuple(_cfg_from_json(v) for v in d['__tuple__'])
+        return {k: _cfg_from_json(v) for k, v in d.items()}
+    if isinstance(d, list):
+        return [_cfg_from_json(v) for v in d]
+    return d
+
+
+def load_ref_configs():
+    """tests/golden/ref_configs.json: the sections of the reference's configs/lsnet/*.py as its own mmcv.Config loads
+    them (oracle/ref_harness/make_golden.py::golden_ref_configs), tuples restored.  {file name: {section: dict}}"""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_configs.json')) as f:
+        return {k: _cfg_from_json(v) for k, v in json.load(f).items()}
+
+
+def nms_cases():
+    """Boxes of tests/test_oracle.py::test_nms_against_reference_build: (n, threshold, dets [n, 5]) with duplicated boxes
+    but no score ties (the reference orders ties by an unstable sort)."""
+    g = torch.Generator().manual_seed(11)
+    out = []
+    for n, thr in ((1, 0.5), (37, 0.3), (500, 0.5), (2000, 0.65)):
+        xy = torch.rand(n, 2, generator=g) * 200
+        wh = torch.rand(n, 2, generator=g) * 60 + 1
+        sc = torch.rand(n, 1, generator=g)
+        if n > 30:
+            xy[20:23], wh[20:23] = xy[20], wh[20]
+        out.append((n, thr, torch.cat([xy, xy + wh, sc], 1)))
+    return out

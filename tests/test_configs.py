@@ -6,6 +6,7 @@ import pytest
 
 from lsnet_amd.model_zoo import build_lsnet, lsnet_config
 from lsnet_amd.utils import Config
+from tests import golden_util as gu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF_CFG = '/root/reference/code/configs/lsnet'
@@ -36,7 +37,6 @@ def test_all_reference_lsnet_configs_load():
         assert 'train_cfg' in cfg and 'test_cfg' in cfg and cfg.optimizer.type == 'SGD'
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference configs are not on this machine')
 @pytest.mark.parametrize('fname,task,backbone', [
     ('lsnet_bbox_r50_fpn_1x_coco.py', 'bbox', 'r50'),
     ('lsnet_segm_r50_fpn_1x_coco.py', 'segm', 'r50'),
@@ -46,8 +46,9 @@ def test_all_reference_lsnet_configs_load():
     ('lsnet_bbox_cpv_x101_fpn_dconv_c3-c5_mstrain_2x_coco.py', 'bbox_cpv', 'x101-dcn'),
 ])
 def test_model_zoo_equals_reference_config(fname, task, backbone):
-    """The zoo is what bench.py uses on the GPU box (no config files there): same model dicts."""
-    ref = Config.fromfile(os.path.join(REF_CFG, fname))
+    """The zoo is what bench.py uses on the GPU box (no config files there): same model dicts as the reference's config
+    files (their sections as the reference loads them: tests/golden/ref_configs.json)."""
+    ref = Config(gu.load_ref_configs()[fname])
     zoo = lsnet_config(task, backbone)
 
     def norm(d):   # tuples vs lists and ConfigDict vs dict do not matter
@@ -82,15 +83,17 @@ def test_registry_builds_every_variant(task, backbone, params_m):
     assert any(n_.startswith('backbone.layer1') for n_ in frozen) and not any('layer2' in n_ for n_ in frozen)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference configs are not on this machine')
 def test_data_sections_of_reference_configs_build():
     """Every `data.train/val/test` pipeline of configs/lsnet/*.py is made of stages this package registers, with the
-    arguments those files pass (the dataset classes themselves need the annotation files, so only the type is checked)."""
+    arguments those files pass (the dataset classes themselves need the annotation files, so only the type is checked).
+    The sections as the reference loads them: tests/golden/ref_configs.json."""
     from lsnet_amd.data import DATASETS, Compose
     from lsnet_amd.utils import Config
     seen = set()
-    for f in sorted(os.listdir(REF_CFG)):
-        cfg = Config.fromfile(os.path.join(REF_CFG, f))
+    refs = gu.load_ref_configs()
+    assert len(refs) == 17
+    for f in sorted(refs):
+        cfg = Config(refs[f])
         for split in ('train', 'val', 'test'):
             d = cfg.data[split]
             assert d['type'] in DATASETS, (f, d['type'])

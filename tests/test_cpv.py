@@ -3,6 +3,7 @@ detector end to end on CPU (native ops served by the oracle backend = test infra
 against the reference in tests/test_golden_host.py::test_cpv_head_forward_loss_backward_decode."""
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -12,15 +13,6 @@ from lsnet_amd.core import PointGenerator, PointHMAssigner, gaussian_radius
 from lsnet_amd.models.losses import GaussianFocalLoss, SEPFocalLoss, SmoothL1Loss
 from lsnet_amd.ops.corner_pool import CornerPool
 from tests import golden_util as gu
-
-HAVE_REF = os.path.isdir('/root/reference/code')
-
-
-def _ref():
-    os.environ['PYTHONDONTWRITEBYTECODE'] = '1'
-    from oracle.ref_harness import bootstrap
-    bootstrap.load_reference()
-
 
 def test_corner_pool_is_a_running_max_towards_the_border():
     x = torch.randn(2, 3, 5, 7, dtype=torch.float64, requires_grad=True)
@@ -102,15 +94,21 @@ def test_corner_heatmap_targets():
     assert empty[0].sum() == 0 and empty[2].numel() == 0 and empty[3].numel() == pts.shape[0]
 
 
-@pytest.mark.skipif(not HAVE_REF, reason='the reference tree is not on this machine')
 def test_corner_heatmap_assigner_equals_reference():
-    _ref()
-    from mmdet.core.bbox.assigners.point_hm_assigner import PointHMAssigner as Ref
+    """Against the reference's PointHMAssigner on the same points and boxes (tests/golden/cpv_assigner.npz, every output
+    in full)."""
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'cpv_assigner.npz'))
+
+    def Ref(bump, _r):
+        return types.SimpleNamespace(assign=lambda p, b, l: [torch.from_numpy(ref[f'{tag}/{i}'])
+                                                             for i in range(len([k for k in ref if k.startswith(tag + '/')]))])
     pts = _points(384, 512)
     for seed, n in ((1, 5), (2, 9), (3, 1), (4, 30)):           # 30 boxes: many shared cells on the coarse levels
         b, l, _ = gu.make_gt(seed, n, 384, 512, num_classes=8)
         for bump in (True, False):
+            tag = f'{seed}/{int(bump)}'
             want, got = Ref(bump, 0.7).assign(pts, b, l), PointHMAssigner(bump, 0.7).assign(pts, b, l)
+            assert len(want) == len(got), (seed, bump)
             for i, (x, y) in enumerate(zip(want, got)):
                 assert x.dtype == y.dtype and x.shape == y.shape, (seed, bump, i)
                 if x.dtype == torch.float32:
@@ -118,7 +116,10 @@ def test_corner_heatmap_assigner_equals_reference():
                 else:
                     assert torch.equal(x, y), (seed, bump, i)
     keep = torch.rand(pts.shape[0], generator=gu.gen(0)) < 0.7   # a filtered point set (cells outside the image)
-    for x, y in zip(Ref(True, 0.7).assign(pts[keep], b, l), PointHMAssigner(True, 0.7).assign(pts[keep], b, l)):
+    tag = 'keep'
+    want, got = Ref(True, 0.7).assign(pts[keep], b, l), PointHMAssigner(True, 0.7).assign(pts[keep], b, l)
+    assert len(want) == len(got)
+    for x, y in zip(want, got):
         assert torch.allclose(x.float(), y.float(), rtol=1e-6, atol=1e-7)
 
 
@@ -182,48 +183,29 @@ def test_cpv_detector_trains_and_tests_from_coco_files(tmp_path, cpu_oracle_back
     assert scatter is not None
 
 
-@pytest.mark.skipif(not HAVE_REF, reason='the reference tree is not on this machine')
 @pytest.mark.parametrize('case', ['empty', 'ragged'])
 @pytest.mark.parametrize('kind', ['bbox', 'cpv'])
 def test_target_edge_cases_equal_reference(kind, case, cpu_oracle_backend):
     """Edge cases of the target builders: one image of the batch has no objects ('empty'); one image is smaller than
     the padded batch, so part of every level's grid lies outside it and is masked out ('ragged').  Both heads against
-    the reference's, run live in the harness on the same weights and inputs."""
+    the reference's on the same weights and inputs (tests/golden/edge_targets.npz: its losses)."""
     import copy
-    _ref()
-    import mmcv
-    from mmdet.models import build_head as ref_build
     from lsnet_amd.models import build_head
     from lsnet_amd.utils import ConfigDict
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'edge_targets.npz'))
     cfg, tr, te = gu.cpv_head_cfg() if kind == 'cpv' else gu.head_cfg('bbox')
-    rc = mmcv.Config(copy.deepcopy(cfg))._cfg_dict
-    rc.update(train_cfg=mmcv.Config(tr), test_cfg=mmcv.Config(te))
     mc = ConfigDict(copy.deepcopy(cfg))
     mc.update(train_cfg=ConfigDict(tr), test_cfg=ConfigDict(te))
-    heads = [gu.fill_params(ref_build(rc), seed=7).train(), gu.fill_params(build_head(mc), seed=7).train()]
-    h, w = gu.HEAD_IMG
-    b0, l0, e0 = gu.make_gt(100, 4, h, w, num_classes=8)
-    if case == 'empty':
-        boxes, labels, ext = [b0, b0[:0]], [l0, l0[:0]], [e0, e0[:0]]
-        small = (h, w)
+    head = gu.fill_params(build_head(mc), seed=7).train()
+    boxes, labels, ext, metas, sem, wts = gu.edge_case_targets(case)
+    outs = head([f.clone() for f in gu.head_inputs(11)])
+    if kind == 'cpv':
+        losses = head.loss(*outs, boxes, ext, sem, wts, labels, metas)
     else:
-        small = (384, 400)                                 # >= 9 cells on the coarsest level, as ATSS needs
-        b1, l1, e1 = gu.make_gt(101, 3, *small, num_classes=8)
-        boxes, labels, ext = [b0, b1], [l0, l1], [e0, e1]
-    metas = [dict(pad_shape=(h, w, 3), img_shape=(h, w, 3), scale_factor=1.0),
-             dict(pad_shape=small + (3,), img_shape=small + (3,), scale_factor=1.0)]
-    sem, wts = gu.make_sem_maps(boxes, labels, h, w, 8)
-    got = []
-    for i, head in enumerate(heads):
-        outs = head([f.clone() for f in gu.head_inputs(11)])
-        if kind == 'cpv':
-            losses = head.loss(*outs, boxes, ext, sem, wts, labels, metas)
-        elif i == 0:
-            losses = head.loss(*outs, gt_bboxes=boxes, gt_extremes=ext, gt_keypoints_vs=None, gt_masks=None,
-                               gt_labels=labels, img_metas=metas)
-        else:
-            losses = head.loss(*outs, boxes, ext, None, None, labels, metas)
-        got.append({k: np.array([float(x) for x in (v if isinstance(v, (list, tuple)) else [v])]) for k, v in losses.items()})
+        losses = head.loss(*outs, boxes, ext, None, None, labels, metas)
+    tag = f'{kind}/{case}/'
+    got = [{k[len(tag):]: ref[k] for k in ref if k.startswith(tag)},
+           {k: np.array([float(x) for x in (v if isinstance(v, (list, tuple)) else [v])]) for k, v in losses.items()}]
     assert sorted(got[0]) == sorted(got[1])
     for k in got[0]:
         assert np.allclose(got[0][k], got[1][k], rtol=1e-4, atol=1e-6), (k, got[0][k], got[1][k])

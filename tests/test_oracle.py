@@ -1,5 +1,7 @@
 """Pins the CPU oracle (oracle/lsnet_oracle.c): analytic identities, an independent differentiable
 torch restatement, and the reference's own known-answer vectors for NMS."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -108,17 +110,9 @@ def test_focal_against_python_formula():
 
 
 def test_nms_against_reference_build():
-    """orc_nms vs the reference's own nms_cpu.cpp compiled into oracle/_ref (oracle/build_ref.py)."""
-    from oracle import build_ref
-    if build_ref.build() is None:
-        pytest.skip('no /root/reference and no prebuilt oracle/_ref/nms_ext.so')
-    ref = build_ref.load()
-    g = torch.Generator().manual_seed(11)
-    for n, thr in ((1, 0.5), (37, 0.3), (500, 0.5), (2000, 0.65)):
-        xy = torch.rand(n, 2, generator=g) * 200
-        wh = torch.rand(n, 2, generator=g) * 60 + 1
-        sc = torch.rand(n, 1, generator=g)
-        if n > 30:   # duplicated boxes (score ties are excluded: the reference orders them by an unstable sort)
-            xy[20:23], wh[20:23] = xy[20], wh[20]
-        dets = torch.cat([xy, xy + wh, sc], 1)
-        assert orc.nms(dets, thr).tolist() == ref.nms(dets, thr).tolist(), (n, thr)
+    """orc_nms vs the reference's own nms_cpu.cpp compiled into oracle/_ref (oracle/build_ref.py): its kept indices on
+    the same boxes (tests/golden/nms_refbuild.npz)."""
+    from tests import golden_util as gu
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'nms_refbuild.npz'))
+    for n, thr, dets in gu.nms_cases():
+        assert orc.nms(dets, thr).tolist() == ref[f'{n}/{thr}'].tolist(), (n, thr)
