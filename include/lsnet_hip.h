@@ -128,9 +128,16 @@ int lsn_version(void);
  *                   (tests: <= 1e-6 of the output range).  2516 / 6 = 419 TFLOP/s peak against 157 for fp32 MFMA.
  * LSN_MATH_BF16X3 : two bf16 values per operand (16 mantissa bits), products h*h + h*l + l*h: relative error
  *                   <= 2^-16 per product (the reference's tolerance for this path is 1e-3).  Opt-in.
- * Process-wide; the initial value comes from the environment variable LSNET_MATH (fp32 | bf16x3 | bf16x6).
- * Kernels without a split variant keep using fp32 MFMA. */
-enum { LSN_MATH_FP32 = 0, LSN_MATH_BF16X3 = 1, LSN_MATH_BF16X6 = 2 };
+ * LSN_MATH_BF16   : every fp32 operand of a contraction is rounded to bf16 by round-to-nearest-even (exactly the h
+ *                   plane of the split modes, v_cvt_pk_bf16_f32) and a product is ONE h*h bf16 MFMA with fp32
+ *                   accumulation: relative error <= 2^-8 per product, the bf16 matrix rate.  Opt-in (mmdet's `fp16`
+ *                   config key).  Tensors in memory stay fp32; epilogues, bias, residual, gates, stream-K fix-ups and
+ *                   reduces stay fp32.
+ * Process-wide; the initial value comes from the environment variable LSNET_MATH (fp32 | bf16 | bf16x3 | bf16x6).
+ * The split modes and LSN_MATH_BF16 cover the same kernels.  Kernels without a split variant keep their arithmetic in
+ * every mode: fp32 MFMA / fmaf chains in the grouped convolutions (lsn_gconv*, the grouped deformable kernels), the
+ * per-anchor gather of the deformable backward, normalisation and the losses. */
+enum { LSN_MATH_FP32 = 0, LSN_MATH_BF16X3 = 1, LSN_MATH_BF16X6 = 2, LSN_MATH_BF16 = 3 };
 int lsn_set_math_mode(int mode);
 int lsn_get_math_mode(void);
 
@@ -329,7 +336,7 @@ int lsn_nms(const float *dets, const int64_t *order, int n, float iou_thr, int64
  * fpn.py:171-217, lsnet_head.py:160-257).  x (B,H,W,C), w (Co,kh,kw,C) = the channels-last image of the
  * (Co,C,kh,kw) weight, out (B,Ho,Wo,Co), fp32, 16-byte aligned; cross-correlation with zero padding like
  * F.conv2d.  Arithmetic: split-bf16 products with fp32 accumulation -- LSN_MATH_BF16X6 (fp32-equivalent) unless the
- * mode is LSN_MATH_BF16X3; there is no fp32-MFMA variant of these kernels (in LSN_MATH_FP32 the Python mirror keeps
+ * mode is LSN_MATH_BF16X3 or LSN_MATH_BF16 (one product); there is no fp32-MFMA variant of these kernels (in LSN_MATH_FP32 the Python mirror keeps
  * the vendor library).  `relu` fuses max(., 0).  Supported: C % 4 == 0; tensors < 2 GiB.
  *
  * The kernels read the weight as a PREPARED IMAGE: bf16 planes in MFMA fragment order, which a wave fetches straight

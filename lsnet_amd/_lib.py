@@ -204,13 +204,13 @@ def scratch_stats():
     return dict(mallocs=int(out[0]), held_bytes=int(out[1]), blocking_syncs=int(out[2]), pool_allocs=int(out[3]))
 
 
-MATH_FP32, MATH_BF16X3, MATH_BF16X6 = 0, 1, 2
-_MODES = {'fp32': MATH_FP32, 'bf16x3': MATH_BF16X3, 'bf16x6': MATH_BF16X6}
+MATH_FP32, MATH_BF16X3, MATH_BF16X6, MATH_BF16 = 0, 1, 2, 3
+_MODES = {'fp32': MATH_FP32, 'bf16x3': MATH_BF16X3, 'bf16x6': MATH_BF16X6, 'bf16': MATH_BF16}
 
 
 def set_math_mode(mode):
-    """'bf16x6' (fp32-equivalent split products, the default), 'bf16x3' or 'fp32' (exact fp32 MFMA);
-    see include/lsnet_hip.h."""
+    """'bf16x6' (fp32-equivalent split products, the default), 'bf16x3', 'bf16' (one product of the bf16-rounded
+    operands, fp32 accumulation) or 'fp32' (exact fp32 MFMA); see include/lsnet_hip.h."""
     check(load().lsn_set_math_mode(_MODES[mode] if isinstance(mode, str) else mode))
 
 
@@ -220,5 +220,5 @@ def get_math_mode():
 
 
 def split_math():
-    """True when the contractions run as split-bf16 products on the matrix pipe (either split mode)."""
+    """True when the contractions run as bf16 products on the matrix pipe ('bf16x6', 'bf16x3' or 'bf16')."""
     return get_math_mode() != 'fp32'

@@ -107,9 +107,18 @@ __device__ __forceinline__ void split3_bf16x2(float v0, float v1, unsigned &hi, 
     lo = cvt_pk_bf16(s0, s1);
 }
 
-// NP = number of bf16 products per fp32 product (3: "bf16x3", 6: "bf16x6"); planes per operand and the
+// ---- single bf16 products ("bf16") ------------------------------------------------------------------
+// a*b = h*h with h = bf16(a) by round-to-nearest-even (the hi plane of the splits above): one bf16 MFMA per product,
+// fp32 accumulation; relative error <= 2^-8 per product.  Peak: the bf16 matrix rate, 2516 TFLOP/s.
+
+// NP = number of bf16 products per fp32 product (1: "bf16", 3: "bf16x3", 6: "bf16x6"); planes per operand and the
 // (A plane, B plane) of product q.  Small terms are issued last so that a consumer may stop early.
 template <int NP> struct SplitCfg;
+template <> struct SplitCfg<1> {
+    static constexpr int NPL = 1;
+    __host__ __device__ static constexpr int pa(int) { return 0; }
+    __host__ __device__ static constexpr int pb(int) { return 0; }
+};
 template <> struct SplitCfg<3> {
     static constexpr int NPL = 2;
     __host__ __device__ static constexpr int pa(int q) { return q == 2 ? 1 : 0; }
@@ -128,10 +137,31 @@ template <> struct SplitCfg<6> {
 template <int NPL>
 __device__ __forceinline__ void split_planes(float v0, float v1, unsigned (&p)[NPL])
 {
-    if constexpr (NPL == 2)
+    if constexpr (NPL == 1)
+        p[0] = cvt_pk_bf16(v0, v1);
+    else if constexpr (NPL == 2)
         split_bf16x2(v0, v1, p[0], p[1]);
     else
         split3_bf16x2(v0, v1, p[0], p[1], p[2]);
+}
+
+// Planes per operand of the product count np of a split mode; 0 for any other value (callers dispatch through
+// split_dispatch, which refuses it).
+__host__ __device__ constexpr int split_npl(int np) { return np == 1 ? 1 : np == 3 ? 2 : np == 6 ? 3 : 0; }
+
+template <int NP> struct SplitNp {
+    static constexpr int value = NP;
+};
+// f(SplitNp<NP>()) for the product count np of a split mode.  Every mode is named here; any other value is an error and
+// never runs another instantiation (a plane-count mismatch between an image and its reader is an out-of-bounds read).
+template <class F> inline int split_dispatch(int np, F &&f)
+{
+    switch (np) {
+    case 1: return f(SplitNp<1>());
+    case 3: return f(SplitNp<3>());
+    case 6: return f(SplitNp<6>());
+    default: return fail(LSN_ERR_INVALID, "no split-bf16 kernels for %d products per product", np);
+    }
 }
 
 // XCD-aware work order.  Workgroups are dealt round-robin to the 8 XCDs (linear id b -> XCD b % 8), each with its

@@ -1,6 +1,6 @@
 // Dense 2-D convolution (groups = 1) on channels-last fp32 tensors as an implicit GEMM on the bf16 matrix pipe with
 // split operands (common.h: NP = 6 products of exact 3-way bf16 splits = fp32-equivalent, the default; NP = 3 products
-// of 2-way splits), fp32 accumulation.  Kernels: conv_kernels.h.
+// of 2-way splits; NP = 1 product of the bf16-rounded operands), fp32 accumulation.  Kernels: conv_kernels.h.
 //
 // The reference runs torch.nn.Conv2d = cuDNN for every dense conv of the path (backbone resnet.py:624-631,
 // 261-301; neck fpn.py:171-217; head lsnet_head.py:160-257).
@@ -29,8 +29,18 @@
 namespace lsn {
 
 int split_np();   // dcn.hip: bf16 products per fp32 product of the current math mode (0: exact fp32)
-static int conv_np() { return split_np() == 3 ? 3 : 6; }   // these kernels have no fp32-MFMA variant: exact mode gets x6
-static int conv_npl() { return conv_np() == 3 ? 2 : 3; }
+// bf16 products of these kernels; they have no fp32-MFMA variant: exact mode gets x6.  -1: no kernels (split_dispatch refuses)
+static int conv_np()
+{
+    switch (split_np()) {
+    case 0: return 6;
+    case 1: return 1;
+    case 3: return 3;
+    case 6: return 6;
+    default: return -1;
+    }
+}
+static int conv_npl() { return split_npl(conv_np()); }
 
 // Library-owned scratch for the partial tiles of split reductions: ONE block PER STREAM (callers on different streams must
 // not share partial tiles), grown on demand.  A block that is outgrown is
@@ -349,13 +359,15 @@ static int launch_conv(ConvArgs &a, int ks, hipStream_t st)
 {
     if constexpr (TN == 2 && WN == 2) {   // the unaligned-slab variant exists for the 64 x 128 tile
         if (a.C % 4 != 0 || a.xpitch % 4 != 0)
-            return conv_np() == 3 ? launch_conv_cfg<TM, TN, WM, WN, 3, true, false>(a, ks, st)
-                                  : launch_conv_cfg<TM, TN, WM, WN, 6, true, false>(a, ks, st);
+            return split_dispatch(conv_np(), [&](auto np) {
+                return launch_conv_cfg<TM, TN, WM, WN, decltype(np)::value, true, false>(a, ks, st);
+            });
     }
     if (a.C % 4 != 0 || a.xpitch % 4 != 0)
         return fail(LSN_ERR_UNSUPPORTED, "conv2d: C %% 4 != 0 needs more than 64 output channels");
-    return conv_np() == 3 ? launch_conv_cfg<TM, TN, WM, WN, 3, false, FINE>(a, ks, st)
-                          : launch_conv_cfg<TM, TN, WM, WN, 6, false, FINE>(a, ks, st);
+    return split_dispatch(conv_np(), [&](auto np) {
+        return launch_conv_cfg<TM, TN, WM, WN, decltype(np)::value, false, FINE>(a, ks, st);
+    });
 }
 
 // Tile choice (pixels x output channels per workgroup; two workgroups share a CU, so the chip holds 512 of them at
@@ -428,8 +440,9 @@ int conv_mm_rows(int n, const float *const *x, float *const *out, const int *row
 #ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
         return conv_forward(a, st);
 #else
-        return conv_np() == 3 ? launch_conv_cfg<2, 2, 1, 4, 3, false, true, true>(a, 1, st)
-                              : launch_conv_cfg<2, 2, 1, 4, 6, false, true, true>(a, 1, st);
+        return split_dispatch(conv_np(), [&](auto np) {
+            return launch_conv_cfg<2, 2, 1, 4, decltype(np)::value, false, true, true>(a, 1, st);
+        });
 #endif
     }
     return conv_forward(a, st);
@@ -450,17 +463,17 @@ static void wfrag_job(WfragJob &j, const float *w, unsigned short *out, int Co, 
     j.bn_gamma = bn.gamma, j.bn_var = bn.var, j.bn_beta = bn.beta, j.bn_mean = bn.mean, j.shift_out = bn.shift_out, j.bn_eps = bn.eps;
 }
 
-static void conv_wfrag(const float *w, unsigned short *out, int Co, int K, int C, int flipT, const TapSub &ts, hipStream_t st,
-                       const BnFold &bn = BnFold())
+static int conv_wfrag(const float *w, unsigned short *out, int Co, int K, int C, int flipT, const TapSub &ts, hipStream_t st,
+                      const BnFold &bn = BnFold())
 {
     WfragJob j;
     wfrag_job(j, w, out, Co, K, C, flipT, ts, bn);
     const long long total = wfrag_threads(j);
     const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (conv_npl() == 2)
-        hipLaunchKernelGGL(conv_wfrag_kernel<2>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, j);
-    else
-        hipLaunchKernelGGL(conv_wfrag_kernel<3>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, j);
+    return split_dispatch(conv_np(), [&](auto np) {
+        hipLaunchKernelGGL(conv_wfrag_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, j);
+        return 0;
+    });
 }
 
 // prof.h span of one launch: 2 P Co C K flops; every operand once (the strided backward-data pass counts grad_out once
@@ -726,15 +739,18 @@ static int prepare_weights(int kind, const float *w, void *prepared, int C, int 
     if (prepared_bytes(kind, C, Co, kh, kw, stride, pad, dil) >= ((int64_t)1 << 31))
         return fail(LSN_ERR_UNSUPPORTED, "conv2d: weight too large for 32-bit buffer offsets");
     if (kind == 0) {
-        conv_wfrag(w, reinterpret_cast<unsigned short *>(prepared), Co, kh * kw, C, 0, TapSub{}, st, bn);
+        if (int rc = conv_wfrag(w, reinterpret_cast<unsigned short *>(prepared), Co, kh * kw, C, 0, TapSub{}, st, bn)) return rc;
     } else if (kind == 2) {
-        conv_wfrag(w, reinterpret_cast<unsigned short *>(prepared), kh * kw * C, 1, Co, 1, TapSub{0, 1, 1, 0, 1, 1, 1}, st, bn);
+        if (int rc = conv_wfrag(w, reinterpret_cast<unsigned short *>(prepared), kh * kw * C, 1, Co, 1, TapSub{0, 1, 1, 0, 1, 1, 1}, st,
+                                bn))
+            return rc;
     } else {
         BwdPlan pl;
         if (int rc = bwd_plan(C, Co, kh, kw, stride, pad, dil, &pl)) return rc;
         for (int ci = 0; ci < pl.ncls; ++ci)
-            conv_wfrag(w, reinterpret_cast<unsigned short *>(reinterpret_cast<unsigned char *>(prepared) + pl.cls[ci].wf_off),
-                       C, kh * kw, Co, 1, pl.cls[ci].ts, st, bn);
+            if (int rc = conv_wfrag(w, reinterpret_cast<unsigned short *>(reinterpret_cast<unsigned char *>(prepared) + pl.cls[ci].wf_off),
+                                    C, kh * kw, Co, 1, pl.cls[ci].ts, st, bn))
+                return rc;
     }
     LSN_HIP(hipGetLastError());
     return 0;
@@ -786,17 +802,17 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     // the fine MFMA / staging interleave (conv_wgrad_kernels.h FINE; round-4 A/B over the step's layer shapes 3.57 -> 3.41 ms)
     // wherever it compiles without spills: not the unaligned form, not the 4 x 1 wave layout of the narrow 3x3 form
     constexpr bool FINE = !(TG == 9 && WI == 4);
-    if constexpr (UN_OK) {
-        if (un)
-            rc = npl == 2 ? launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 3, true, PMAX, false>)
-                          : launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 6, true, PMAX, false>);
-        else
-            rc = npl == 2 ? launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 3, false, PMAX, FINE>)
-                          : launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 6, false, PMAX, FINE>);
-    } else {
-        rc = npl == 2 ? launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 3, false, PMAX, FINE>)
-                      : launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, 6, false, PMAX, FINE>);
-    }
+    rc = split_dispatch(conv_np(), [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        if constexpr (NP == 1 && TG == 9 && WI == 4) {   // (not instantiated: see conv_wgrad_mm)
+            return fail(LSN_ERR_INVALID, "conv2d backward-weight: no one-product form of the narrow 3x3 kernel");
+        } else {
+            if constexpr (UN_OK) {
+                if (un) return launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, NP, true, PMAX, false>);
+            }
+            return launch(conv_wgrad_kernel<TI, TJ, TG, WI, WJ, NP, false, PMAX, FINE>);
+        }
+    });
     if (rc) return rc;
     return conv_wgrad_reduce(a.part, gw, nW, a.part_b, gb, a.Co, S, S, accumulate, st);
 }
@@ -969,6 +985,9 @@ int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, 
     a.cstep = kw == 1 ? stride : 1;
     a.PW = kw == 1 ? 16 : 15 * stride + (kw - 1) * dil + 1;
     if (kh * a.PW > 99) return 1;
+    // (the narrow 3x3 form's 4 x 1 wave layout spills registers with one product per tap -- tools/kernel_resources.sh: 256
+    // VGPRs + 7 .. 9 spilled -- so LSN_MATH_BF16 leaves those layers to the general kernel of dcn.hip)
+    if (kh * kw == 9 && Co <= 32 && conv_np() == 1) return 1;
     double px = 0, in_el = 0;
     for (int i = 0; i < n; ++i) px += (double)a.lv[i].B * a.lv[i].Ho * a.lv[i].Wo, in_el += (double)a.lv[i].B * a.lv[i].H * a.lv[i].W * C;
     ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * Co * C * kh * kw, 4.0 * (in_el + px * Co + (double)Co * kh * kw * C), st);
@@ -1044,10 +1063,12 @@ static int prepare_weights_multi(int n, const lsn_conv_wprep *it, hipStream_t st
         g_jobs_host = jobs;
     }
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (conv_npl() == 2)
-        hipLaunchKernelGGL(conv_wfrag_multi_kernel<2>, dim3(blocks), dim3(256), 0, st, g_jobs_dev, (int)jobs.size(), total);
-    else
-        hipLaunchKernelGGL(conv_wfrag_multi_kernel<3>, dim3(blocks), dim3(256), 0, st, g_jobs_dev, (int)jobs.size(), total);
+    if (int rc = split_dispatch(conv_np(), [&](auto np) {
+            hipLaunchKernelGGL(conv_wfrag_multi_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(blocks), dim3(256), 0, st, g_jobs_dev,
+                               (int)jobs.size(), total);
+            return 0;
+        }))
+        return rc;
     LSN_HIP(hipGetLastError());
     return 0;
 }

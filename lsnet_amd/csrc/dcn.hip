@@ -41,12 +41,22 @@ static int math_mode()
         const char *e = getenv("LSNET_MATH");
         g_math_mode = (e && (!strcmp(e, "fp32") || !strcmp(e, "exact"))) ? LSN_MATH_FP32
                       : (e && !strcmp(e, "bf16x3"))                       ? LSN_MATH_BF16X3
+                      : (e && !strcmp(e, "bf16"))                         ? LSN_MATH_BF16
                                                                           : LSN_MATH_BF16X6;
     }
     return g_math_mode;
 }
-// bf16 products per fp32 product of the current mode (0: exact fp32 MFMA)
-static int math_np() { return math_mode() == LSN_MATH_BF16X6 ? 6 : (math_mode() == LSN_MATH_BF16X3 ? 3 : 0); }
+// bf16 products per fp32 product of the current mode (0: exact fp32 MFMA; -1: unknown, which split_dispatch refuses)
+static int math_np()
+{
+    switch (math_mode()) {
+    case LSN_MATH_FP32: return 0;
+    case LSN_MATH_BF16: return 1;
+    case LSN_MATH_BF16X3: return 3;
+    case LSN_MATH_BF16X6: return 6;
+    default: return -1;
+    }
+}
 int split_np() { return math_np(); }
 void dbg_state(long long **buf, int *block) { *buf = g_dbg_buf, *block = g_dbg_block; }
 
@@ -262,7 +272,7 @@ static bool mm_common_ok(const DcnArgs &a)
     return true;
 }
 
-static int mm_npl() { return math_np() == 6 ? 3 : 2; }
+static int mm_npl() { return split_npl(math_np()); }
 
 static bool mm_fwd_ok(const DcnArgs &a)
 {
@@ -299,10 +309,11 @@ static int mm_prepare_weights(DcnArgs &a, bool backward, void *dst, hipStream_t 
         j.w = a.w, j.out = out, j.Co = Co, j.K = Kd, j.C = C, j.flipT = backward ? 1 : 0, j.ts = ts;
         const long long total = wfrag_threads(j);
         const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (mm_npl() == 3)
-            hipLaunchKernelGGL(conv_wfrag_kernel<3>, dim3(blocks), dim3(256), 0, st, j);
-        else
-            hipLaunchKernelGGL(conv_wfrag_kernel<2>, dim3(blocks), dim3(256), 0, st, j);
+        if (int rc = split_dispatch(math_np(), [&](auto np) {
+                hipLaunchKernelGGL(conv_wfrag_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(blocks), dim3(256), 0, st, j);
+                return 0;
+            }))
+            return rc;
         LSN_HIP(hipGetLastError());
     }
     a.wtp = out;
@@ -370,8 +381,10 @@ static int launch_forward_mm(const DcnArgs &a, hipStream_t st)
     // (the 64 x 256 tile in the fine MFMA / staging interleave, dcn_mm_kernels.h FINE: tower launch 310 -> 280 us, pyramid
     // 818 -> 780 us in the round-4 A/B, profiles/r4_fine.txt)
     const bool wide = a.Co % 256 == 0;
-    if (math_np() == 6) return wide ? launch_fwd_mm_cfg<2, 2, 1, 4, 6, true>(a, st) : launch_fwd_mm_cfg<1, 2, 2, 2, 6>(a, st);
-    return wide ? launch_fwd_mm_cfg<2, 2, 1, 4, 3, true>(a, st) : launch_fwd_mm_cfg<1, 2, 2, 2, 3>(a, st);
+    return split_dispatch(math_np(), [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        return wide ? launch_fwd_mm_cfg<2, 2, 1, 4, NP, true>(a, st) : launch_fwd_mm_cfg<1, 2, 2, 2, NP>(a, st);
+    });
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -449,21 +462,23 @@ static int launch_forward(const DcnArgs &a, hipStream_t st)
     if (grouped_fwd_ok(a)) return launch_forward_grouped(a, st);
     const int np = math_np(), KDf = a.kh * a.kw * a.dg;
     // exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU
-    if (np == 0 || !xn_ok(a) || (np == 6 ? xn_lds_bytes<6>(KDf) : xn_lds_bytes<3>(KDf)) > 160 * 1024) {
+    if (np == 0 || !xn_ok(a) || xn_lds_bytes(split_npl(np), KDf) > 160 * 1024) {
         ProfScope prof(PROF_FWD, a, st);
         return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, st) : launch_forward_t<64, 256, 1, 4>(a, st);
     }
     dim3 grid(a.ntiles, cdiv(a.Co / a.groups, PIPE_BN), a.groups);
     ProfScope prof(PROF_FWD, a, st);
-    const size_t ldsn = np == 6 ? xn_lds_bytes<6>(KDf) : xn_lds_bytes<3>(KDf);
-    auto gox = [&](auto kern) -> int {
+    auto gox = [&](auto kern, size_t ldsn) -> int {
         if (int rc = set_lds(kern, ldsn)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(256), ldsn, st, a);
         LSN_HIP(hipGetLastError());
         return 0;
     };
-    if (np == 6) return a.wtp ? gox(dcn_fwd_xn_kernel<true, 6>) : gox(dcn_fwd_xn_kernel<false, 6>);
-    return a.wtp ? gox(dcn_fwd_xn_kernel<true, 3>) : gox(dcn_fwd_xn_kernel<false, 3>);
+    return split_dispatch(np, [&](auto npc) {
+        constexpr int NP = decltype(npc)::value;
+        const size_t ldsn = xn_lds_bytes<NP>(KDf);
+        return a.wtp ? gox(dcn_fwd_xn_kernel<true, NP>, ldsn) : gox(dcn_fwd_xn_kernel<false, NP>, ldsn);
+    });
 }
 
 template <int RED>
@@ -862,8 +877,13 @@ static int launch_bwd_data(DcnArgs &a, void *gather_ws, size_t gather_ws_bytes, 
         gather_plan(a, pl);
         if (pl.ok && pl.bytes <= gather_ws_bytes) {
             unsigned char *ws = reinterpret_cast<unsigned char *>(gather_ws);
-            return np == 3 ? launch_bwd_colbuf<3>(a, pl, ws, st) : np == 6 ? launch_bwd_colbuf<6>(a, pl, ws, st)
-                                                                           : launch_bwd_colbuf<0>(a, pl, ws, st);
+            switch (np) {
+            case 0: return launch_bwd_colbuf<0>(a, pl, ws, st);
+            case 1: return launch_bwd_colbuf<1>(a, pl, ws, st);
+            case 3: return launch_bwd_colbuf<3>(a, pl, ws, st);
+            case 6: return launch_bwd_colbuf<6>(a, pl, ws, st);
+            default: return fail(LSN_ERR_INVALID, "deformable backward: unknown math mode (%d products)", np);
+            }
         }
     }
     if (a.mm) return fail(LSN_ERR_RUNTIME, "deformable backward: fragment-order weights without the gather path");
@@ -879,7 +899,7 @@ static int launch_bwd_data(DcnArgs &a, void *gather_ws, size_t gather_ws_bytes, 
             LSN_HIP(hipGetLastError());
             return 0;
         };
-        return np == 6 ? gox(dcn_bwd_data_xn_kernel<6, false>) : gox(dcn_bwd_data_xn_kernel<3, false>);
+        return split_dispatch(np, [&](auto npc) { return gox(dcn_bwd_data_xn_kernel<decltype(npc)::value, false>); });
     }
     return (a.Co / a.groups > 64) ? launch_bwd_data_t<256>(a, st) : launch_bwd_data_t<64>(a, st);
 }
@@ -966,8 +986,12 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
         hipLaunchKernelGGL(dcn_chunk_meta_kernel, dim3(cdiv(nchunks, 256)), dim3(256), 0, st, a, nchunks, meta);
     }
     ProfScope prof(dense ? -1 : PROF_WGRAD, a, st);
-    auto pre = npl == 3 ? dcn_gout_frag_kernel<3> : dcn_gout_frag_kernel<2>;
-    hipLaunchKernelGGL(pre, dim3(nblk_s, a.Co / 128), dim3(256), 0, st, a, nsteps16, spb, img, a.gb ? part_b : nullptr);
+    if (int rc = split_dispatch(math_np(), [&](auto np) {
+            hipLaunchKernelGGL(dcn_gout_frag_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(nblk_s, a.Co / 128), dim3(256), 0, st, a,
+                               nsteps16, spb, img, a.gb ? part_b : nullptr);
+            return 0;
+        }))
+        return rc;
     const size_t lds = dcn_wgrad_mm_lds_bytes(npl);
     if ((long long)nchunks * (S + 1) >= (1ll << 32))
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward-weight: %d chunks x %d splits exceed the kernel's 32-bit split arithmetic", nchunks, S);
@@ -978,11 +1002,11 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
         return 0;
     };
     // (FINE = the fine MFMA / staging interleave: tower 360 -> 345 us, pyramid 941 -> 916 us, profiles/r4_fine.txt)
-    if (dense) {
-        if (int rc = (math_np() == 6 ? go(dcn_wgrad_mm_kernel<6, true, true>) : go(dcn_wgrad_mm_kernel<3, true, true>))) return rc;
-    } else if (int rc = (math_np() == 6 ? go(dcn_wgrad_mm_kernel<6, false, true>) : go(dcn_wgrad_mm_kernel<3, false, true>))) {
+    if (int rc = split_dispatch(math_np(), [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            return dense ? go(dcn_wgrad_mm_kernel<NP, true, true>) : go(dcn_wgrad_mm_kernel<NP, false, true>);
+        }))
         return rc;
-    }
     return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, S, nblk_s, accumulate ? 1 : 0, st);
 }
 
@@ -1094,27 +1118,20 @@ static int launch_wgrad(const DcnArgs &a_in, int nsteps, bool accumulate, hipStr
         LSN_HIP(hipGetLastError());
         return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
     }
-    if (ordered) {
-        const size_t ldsn = math_np() == 6 ? wgrad_xn_lds_bytes<6>() : wgrad_xn_lds_bytes<3>();
-        auto kern = math_np() == 6 ? dcn_wgrad_xn_kernel<false, 6> : dcn_wgrad_xn_kernel<false, 3>;
-        if (int rc = set_lds(kern, ldsn)) return rc;
-        hipLaunchKernelGGL(kern, dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
-        LSN_HIP(hipGetLastError());
-        return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
-    }
-    if (math_np() && !((g_dbg_block >> 30) & 1)) {   // bit 30: force the fp32 MFMA kernel
-        if (math_np() == 6) {
-            const size_t ldsn = wgrad_xn_lds_bytes<6>();
-            if (int rc = set_lds(dcn_wgrad_xn_kernel<false, 6>, ldsn)) return rc;
-            hipLaunchKernelGGL((dcn_wgrad_xn_kernel<false, 6>), dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
-        } else {
-            const size_t ldsn = wgrad_xn_lds_bytes<3>();
-            if (int rc = set_lds(dcn_wgrad_xn_kernel<false, 3>, ldsn)) return rc;
-            hipLaunchKernelGGL((dcn_wgrad_xn_kernel<false, 3>), dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
-        }
+    auto go_xn = [&](auto np) -> int {
+        constexpr int NP = decltype(np)::value;
+        const size_t ldsn = wgrad_xn_lds_bytes<NP>();
+        if (int rc = set_lds(dcn_wgrad_xn_kernel<false, NP>, ldsn)) return rc;
+        hipLaunchKernelGGL((dcn_wgrad_xn_kernel<false, NP>), dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
         LSN_HIP(hipGetLastError());
         return 0;
+    };
+    if (ordered) {
+        if (int rc = split_dispatch(math_np(), go_xn)) return rc;
+        return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
     }
+    if (math_np() && !((g_dbg_block >> 30) & 1))   // bit 30: force the fp32 MFMA kernel
+        return split_dispatch(math_np(), go_xn);
     if (vec_ok(a))
         hipLaunchKernelGGL(dcn_wgrad_kernel<true>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
     else
@@ -1169,12 +1186,12 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
         if (int rc = mm_prepare_weights(a, false, s.workspace, st, s.weights_prepared != 0)) return rc;
     } else if (s.workspace && math_np() && (Cg % 8 == 0) && a.Co / a.groups > 64 && xn_ok(a)) {
         const size_t nw = (size_t)s.Co * K * Cg;   // split the weights once instead of in every block
-        if (math_np() == 6)
-            hipLaunchKernelGGL(dcn_prepare_w_kernel<3>, dim3(512), dim3(256), 0, st, a.w,
-                               reinterpret_cast<unsigned short *>(s.workspace), nw);
-        else
-            hipLaunchKernelGGL(dcn_prepare_w_kernel<2>, dim3(512), dim3(256), 0, st, a.w,
-                               reinterpret_cast<unsigned short *>(s.workspace), nw);
+        if (int rc = split_dispatch(math_np(), [&](auto np) {
+                hipLaunchKernelGGL(dcn_prepare_w_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(512), dim3(256), 0, st, a.w,
+                                   reinterpret_cast<unsigned short *>(s.workspace), nw);
+                return 0;
+            }))
+            return rc;
         a.wtp = reinterpret_cast<const unsigned short *>(s.workspace);
     }
     if (int rc = launch_forward(a, st)) return rc;
@@ -1264,12 +1281,12 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
         if (mm) {
             if (int rc = mm_prepare_weights(a, true, s.workspace, st, s.weights_prepared != 0)) return rc;
         } else if (can_split) {
-            if (math_np() == 6)
-                hipLaunchKernelGGL(dcn_prepare_wt_kernel<3>, dim3(512), dim3(256), 0, st, a.w,
-                                   reinterpret_cast<unsigned short *>(s.workspace), s.Co, K, s.C);
-            else
-                hipLaunchKernelGGL(dcn_prepare_wt_kernel<2>, dim3(512), dim3(256), 0, st, a.w,
-                                   reinterpret_cast<unsigned short *>(s.workspace), s.Co, K, s.C);
+            if (int rc = split_dispatch(math_np(), [&](auto np) {
+                    hipLaunchKernelGGL(dcn_prepare_wt_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(512), dim3(256), 0, st, a.w,
+                                       reinterpret_cast<unsigned short *>(s.workspace), s.Co, K, s.C);
+                    return 0;
+                }))
+                return rc;
         }
         if (int rc = launch_bwd_data(a, gws, gws_bytes, st)) return rc;
     } else if (a.opitch != a.Co) {
@@ -1468,11 +1485,13 @@ static int conv_wgrad_xn(int n, const lsn_conv_level *lv, float *gw, float *gb, 
     double px = 0, in_el = 0;
     for (int i = 0; i < n; ++i) px += (double)a.lv[i].P, in_el += (double)a.lv[i].B * a.lv[i].H * a.lv[i].W * C;
     ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * Co * C * K, 4.0 * (in_el + px * Co + (double)Co * K * C), st);
-    const bool x3 = math_np() == 3;   // exact-mode callers get the fp32-equivalent split: there is no fp32-MFMA dense wgrad
-    if (Co <= 64)
-        return x3 ? conv_wgrad_launch<3, 64>(a, steps, C, Co, K, accumulate, st) : conv_wgrad_launch<6, 64>(a, steps, C, Co, K, accumulate, st);
-    return x3 ? conv_wgrad_launch<3, 256>(a, steps, C, Co, K, accumulate, st)
-              : conv_wgrad_launch<6, 256>(a, steps, C, Co, K, accumulate, st);
+    // exact-mode callers get the fp32-equivalent split: there is no fp32-MFMA dense wgrad
+    const int np = math_np() == 0 ? 6 : math_np();
+    return split_dispatch(np, [&](auto npc) {
+        constexpr int NP = decltype(npc)::value;
+        return Co <= 64 ? conv_wgrad_launch<NP, 64>(a, steps, C, Co, K, accumulate, st)
+                        : conv_wgrad_launch<NP, 256>(a, steps, C, Co, K, accumulate, st);
+    });
 }
 
 }  // namespace lsn
@@ -1553,7 +1572,8 @@ int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_l
 
 int lsn_set_math_mode(int mode)
 {
-    LSN_CHECK(mode == LSN_MATH_FP32 || mode == LSN_MATH_BF16X3 || mode == LSN_MATH_BF16X6, "unknown math mode %d", mode);
+    LSN_CHECK(mode == LSN_MATH_FP32 || mode == LSN_MATH_BF16X3 || mode == LSN_MATH_BF16X6 || mode == LSN_MATH_BF16,
+              "unknown math mode %d", mode);
     lsn::g_math_mode = mode;
     return 0;
 }

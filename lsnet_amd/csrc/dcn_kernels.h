@@ -460,8 +460,8 @@ constexpr int PIPE_BM = 64, PIPE_BN = 256, PIPE_BK = 32, PIPE_LDK = 36;
 //
 // Same tiling and software pipeline as dcn_fwd_pipe_kernel (64 px x 256 co, one workgroup per CU, chunk t's
 // MFMAs interleaved with the LDS commit of chunk t+1 and the load issue of chunk t+2), but the blended samples and
-// the weights are split into bf16 planes while they are staged (common.h: NP = 3 products on 2 planes, or NP = 6
-// products on 3 planes = fp32-equivalent) and multiplied on v_mfma_f32_32x32x16_bf16.  4 NP MFMAs of 32 cycles per
+// the weights are split into bf16 planes while they are staged (common.h: NP = 1 product on 1 plane, NP = 3 products on
+// 2 planes, or NP = 6 products on 3 planes = fp32-equivalent) and multiplied on v_mfma_f32_32x32x16_bf16.  4 NP MFMAs of 32 cycles per
 // k-step instead of 64 of 64 cycles per chunk, and the VALU work of the staging overlaps them (the bf16 pipe is
 // separate from the fp32 ALUs).
 // LDS rows: 32 k-values = 64 B of bf16, no padding; the four 16-byte slots of row r are stored at slot ^ ((r >> 2) & 3),
@@ -470,10 +470,14 @@ constexpr int PIPE_BM = 64, PIPE_BN = 256, PIPE_BK = 32, PIPE_LDK = 36;
 // =============================================================================================
 constexpr int XN_RS = 64;   // LDS row stride, bytes
 
+__host__ __device__ inline size_t xn_lds_bytes(int npl, int KD)
+{
+    return (size_t)2 * npl * (PIPE_BM + PIPE_BN) * XN_RS + (size_t)PIPE_BM * KD * sizeof(Tap);
+}
 template <int NP>
 __host__ __device__ inline size_t xn_lds_bytes(int KD)
 {
-    return (size_t)2 * SplitCfg<NP>::NPL * (PIPE_BM + PIPE_BN) * XN_RS + (size_t)PIPE_BM * KD * sizeof(Tap);
+    return xn_lds_bytes(SplitCfg<NP>::NPL, KD);
 }
 
 // byte offset of 16-byte slot `slot` of row `row` inside a plane
@@ -609,7 +613,7 @@ __global__ __launch_bounds__(256, 1) void dcn_fwd_xn_kernel(const DcnArgs a)
     // with whole slices in the gaps, 1.9 k with micro-slots).  A pixel slice is therefore cut into five slots of a few
     // instructions -- bilinear blend, split step A (hi plane + residual), split step B (mid / lo planes), the LDS
     // writes, the four corner loads of chunk t+2 into the registers just consumed -- then the weight slices
-    // (commit, issue).
+    // (commit, issue).  With one plane (NP = 1) step A is the rounding alone and step B is empty.
     float sp_v0 = 0.f, sp_v1 = 0.f, sp_r0 = 0.f, sp_r1 = 0.f;
     unsigned sp_h = 0, sp_m = 0, sp_l = 0;
     auto staging_slot = [&](int s, const Chunk &c1, const Chunk &c2, unsigned char *bn) {
@@ -625,11 +629,15 @@ __global__ __launch_bounds__(256, 1) void dcn_fwd_xn_kernel(const DcnArgs a)
             } else if (part == 1) {
                 const bf16x2 h = {(__bf16)sp_v0, (__bf16)sp_v1};
                 sp_h = __builtin_bit_cast(unsigned, h);
-                sp_r0 = sp_v0 - __uint_as_float(sp_h << 16);
-                sp_r1 = sp_v1 - __uint_as_float(sp_h & 0xffff0000u);
+                if constexpr (NPL > 1) {
+                    sp_r0 = sp_v0 - __uint_as_float(sp_h << 16);
+                    sp_r1 = sp_v1 - __uint_as_float(sp_h & 0xffff0000u);
+                }
             } else if (part == 2) {
-                const bf16x2 m = {(__bf16)sp_r0, (__bf16)sp_r1};
-                sp_m = __builtin_bit_cast(unsigned, m);
+                if constexpr (NPL > 1) {
+                    const bf16x2 m = {(__bf16)sp_r0, (__bf16)sp_r1};
+                    sp_m = __builtin_bit_cast(unsigned, m);
+                }
                 if constexpr (NPL == 3) {
                     const float s0 = sp_r0 - __uint_as_float(sp_m << 16), s1 = sp_r1 - __uint_as_float(sp_m & 0xffff0000u);
                     const bf16x2 l = {(__bf16)s0, (__bf16)s1};
@@ -638,7 +646,7 @@ __global__ __launch_bounds__(256, 1) void dcn_fwd_xn_kernel(const DcnArgs a)
             } else if (part == 3) {
                 unsigned char *p = bn + ps * 16 * RS + xcommit;
                 *reinterpret_cast<unsigned *>(p) = sp_h;
-                *reinterpret_cast<unsigned *>(p + PLANE_A) = sp_m;
+                if constexpr (NPL > 1) *reinterpret_cast<unsigned *>(p + PLANE_A) = sp_m;
                 if constexpr (NPL == 3) *reinterpret_cast<unsigned *>(p + 2 * PLANE_A) = sp_l;
             } else {
                 issue_x(c2, ps);
@@ -1052,7 +1060,7 @@ constexpr int BXN_ROW = 512;   // bytes per LDS row of the transposed weight sla
 
 __host__ __device__ inline size_t bwd_xn_lds_bytes(int np, int KD)
 {
-    return (size_t)(np == 6 ? 3 : 2) * 32 * BXN_ROW + (size_t)BWD_BM * KD * (sizeof(Tap) + 12);
+    return (size_t)split_npl(np) * 32 * BXN_ROW + (size_t)BWD_BM * KD * (sizeof(Tap) + 12);
 }
 
 template <int NP, bool COLBUF>
@@ -1505,7 +1513,7 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_kernel(const DcnArgs a, int 
 //
 // Same decomposition as dcn_wgrad_kernel (grid = column blocks x pixel splits x co blocks, 32-pixel steps, fp32 atomics
 // into gw at the end).  The reduction index of this GEMM is the PIXEL, so both LDS images are built pixel-contiguous
-// -- As[co][32 px], Bs[kcol][32 px], NPL bf16 planes each (2 or 3), 80-byte rows -- to give every lane the 8
+// -- As[co][32 px], Bs[kcol][32 px], NPL bf16 planes each (1, 2 or 3), 80-byte rows -- to give every lane the 8
 // consecutive k-values v_mfma_f32_32x32x16_bf16 wants.  A thread owns two adjacent output channels x 16 pixels of
 // grad_output and two adjacent channels x 4 pixels of the gathered columns (8-byte buffer loads, out-of-range rows read
 // as zero), splits its values in registers and writes 16- resp. 8-byte row pieces.  48 (24) bf16 MFMAs per step and wave.

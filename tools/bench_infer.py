@@ -16,7 +16,7 @@ for task in ('pose_kbox', 'bbox'):
     model = model.to(dev).to(memory_format=torch.channels_last).eval()
     img = torch.randn(B, 3, H, W, device=dev).contiguous(memory_format=torch.channels_last)
     metas = [dict(pad_shape=(H, W, 3), img_shape=(H, W, 3), scale_factor=1.0, ori_shape=(H, W, 3), flip=False)] * B
-    for math in ('bf16x3', 'fp32'):
+    for math in ('bf16x3', 'bf16', 'fp32'):
         _lib.set_math_mode(math)
         with torch.no_grad():
             for _ in range(3):
