@@ -542,10 +542,27 @@ typedef struct lsn_gate_job {
 int lsn_relu_gate_multi(int n_jobs, const lsn_gate_job *jobs, lsn_stream_t stream);
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */
-/* When set to a device buffer of 512 int64 (NULL disables), thread 0 of workgroup `block` of the
- * next DCN forward / backward-data launches appends (phase_id << 56 | shader_clock) stamps at its
- * phase boundaries: a per-chunk cycle anatomy for tuning.  Not thread-safe; profiling only. */
-int lsn_debug_phase_clocks(long long *device_buf_512, int block);
+/* The debug word of lsn_debug_phase_clocks.  Bits 0-15 (LSN_DBG_BLOCK_MASK) name the workgroup whose phase clocks are
+ * recorded; bits 16-19 are reserved (they used to select kernels: a word that sets one is refused rather than read as a
+ * workgroup).  Each named bit from 20 up routes the deformable family onto one of its other kernel paths, for tests and
+ * A/B runs; every path computes the same results to the tolerances of the tests.  Word 0 is the product routing. */
+enum {
+    LSN_DBG_BLOCK_MASK = 0xffff,
+    LSN_DBG_ANCHOR_ONE_WAVE = 1 << 20,  /* per-anchor sums: one wave walks every 256-channel block of its anchor   */
+    LSN_DBG_FWD_SK_ALWAYS = 1 << 21,    /* forward: stream-K pieces for launches of any size                      */
+    LSN_DBG_FWD_SK_NEVER = 1 << 22,     /* forward: whole tiles only                                              */
+    LSN_DBG_ATOMIC_SCATTER = 1 << 23,   /* backward-data: the atomic scatter kernels instead of the gather pass   */
+    LSN_DBG_WG_COMPUTED_TAPS = 1 << 24, /* weight gradient: rebuild the sampling table, not the backward's table  */
+    LSN_DBG_WG_SCALAR_LOADS = 1 << 25,  /* weight gradient: scalar loads instead of 8-byte ones                   */
+    LSN_DBG_GENERAL_GEMMS = 1 << 28     /* no kernel of dcn_mm_kernels.h: dcn_kernels.h only, and the dense weight
+                                         * gradient on the patch kernel of conv_wgrad_kernels.h                   */
+};
+/* When device_buf_512 is a device buffer of 512 int64 (NULL disables), thread 0 of workgroup `word & LSN_DBG_BLOCK_MASK`
+ * of the next DCN forward / backward-data launches appends (phase_id << 56 | shader_clock) stamps at its phase
+ * boundaries: a per-chunk cycle anatomy for tuning.  The LSN_DBG_* bits of `word` hold until the next call.  A word that
+ * sets any bit outside LSN_DBG_BLOCK_MASK and the named bits returns LSN_ERR_INVALID and changes nothing.  Not
+ * thread-safe; profiling only. */
+int lsn_debug_phase_clocks(long long *device_buf_512, int word);
 
 /* Per-kernel-family launch timing.  lsn_prof_enable(1) clears the log and makes every launch of the instrumented
  * families record a HIP event pair on its launch stream; lsn_prof_read() waits for the recorded events and returns one

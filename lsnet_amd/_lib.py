@@ -204,6 +204,24 @@ def scratch_stats():
     return dict(mallocs=int(out[0]), held_bytes=int(out[1]), blocking_syncs=int(out[2]), pool_allocs=int(out[3]))
 
 
+# the debug word of lsn_debug_phase_clocks (include/lsnet_hip.h): bits 0-15 the phase-clock workgroup, from bit 20 up the
+# kernel routings that tests and A/B runs select; any other bit is refused
+DBG_BLOCK_MASK = 0xffff
+DBG_ANCHOR_ONE_WAVE = 1 << 20
+DBG_FWD_SK_ALWAYS = 1 << 21
+DBG_FWD_SK_NEVER = 1 << 22
+DBG_ATOMIC_SCATTER = 1 << 23
+DBG_WG_COMPUTED_TAPS = 1 << 24
+DBG_WG_SCALAR_LOADS = 1 << 25
+DBG_GENERAL_GEMMS = 1 << 28
+
+
+def set_debug_word(word, buf=None):
+    """lsn_debug_phase_clocks: `word` = a phase-clock workgroup | DBG_* routing bits, `buf` = the device address of 512
+    int64 for the phase clocks (None: no clocks).  Raises RuntimeError when the library refuses the word."""
+    check(load().lsn_debug_phase_clocks(None if buf is None else ctypes.c_void_p(buf), ctypes.c_int(word)))
+
+
 MATH_FP32, MATH_BF16X3, MATH_BF16X6, MATH_BF16 = 0, 1, 2, 3
 _MODES = {'fp32': MATH_FP32, 'bf16x3': MATH_BF16X3, 'bf16x6': MATH_BF16X6, 'bf16': MATH_BF16}
 

@@ -118,9 +118,5 @@ def build_host(force=False, verbose=False):
 
 
 if __name__ == '__main__':
-    if '--ab' in sys.argv:   # the A/B variant: python build.py --ab [-DNAME ...]
-        print(build(force='--force' in sys.argv, verbose=True, defines=['LSNET_AB=1'] + [a[2:] for a in sys.argv if a.startswith('-D')],
-                    so=os.path.join(HERE, 'liblsnet_hip_ab.so')))
-        sys.exit(0)
     print(build(force='--force' in sys.argv, verbose=True))
     print(build_host(force='--force' in sys.argv, verbose=True))

@@ -222,9 +222,6 @@ int lib_tickets(unsigned **p, hipStream_t st)
 static void sk_plan(int ntw, int Tall, int *n_dp, int *sk_n, int *sk_tiles)
 {
     *n_dp = ntw, *sk_n = 0, *sk_tiles = 0;
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-    return;
-#endif
     constexpr int SLOTS = 512;
     // (launches of two or more whole rounds lose more to the segment loop's longer prologue in EVERY workgroup than the
     // last round can return: profiles/r5_sk_policy.txt, layer-1 rows)
@@ -312,23 +309,6 @@ static int launch_conv_range(ConvArgs &a, int ks, int tile_base, int ntiles, hip
     return 0;
 }
 
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-// Round 4's tail split (the A/B library keeps rounds 3 / 4's work distribution: blockIdx.z splits, this, no stream-K): a
-// single-level launch whose last round would be a small remainder runs its last pixel tiles as a second launch with the
-// reduction split `kt` ways (profiles/r4_tail_split.txt).
-static int tail_split(int total_wg, int colblocks, int Tall, int *tail_tiles)
-{
-    const int rem = total_wg % 512;
-    if (total_wg <= 512 || rem == 0 || rem > 128 || rem % colblocks != 0 || Tall < 48) return 1;
-    int kt = 384 / rem;
-    if (kt > Tall / 4) kt = Tall / 4;
-    if (kt > 16) kt = 16;
-    if (kt < 2) return 1;
-    *tail_tiles = rem / colblocks;
-    return kt;
-}
-#endif
-
 template <int TM, int TN, int WM, int WN, int NP, bool UNAL, bool FINE, bool TRANS = false>
 static int launch_conv_cfg(ConvArgs &a, int ks, hipStream_t st)
 {
@@ -339,16 +319,6 @@ static int launch_conv_cfg(ConvArgs &a, int ks, hipStream_t st)
         tiles += (a.lv[i].P + BM - 1) / BM;
     }
     a.ntiles = tiles;
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-    const int colblocks = (a.Co + BN - 1) / BN;
-    int tail = 0;
-    const int kt = (a.nlv == 1 && !a.ostep && ks == 1 && !TRANS) ? tail_split(tiles * colblocks, colblocks, a.kh * a.kw * cv_ncc(a.C), &tail)
-                                                                : 1;
-    if (kt > 1) {
-        if (int rc = launch_conv_range<TM, TN, WM, WN, NP, UNAL, FINE, TRANS>(a, 1, 0, tiles - tail, st)) return rc;
-        return launch_conv_range<TM, TN, WM, WN, NP, UNAL, FINE, TRANS>(a, kt, tiles - tail, tail, st);
-    }
-#endif
     return launch_conv_range<TM, TN, WM, WN, NP, UNAL, FINE, TRANS>(a, ks, 0, tiles, st);
 }
 
@@ -397,17 +367,8 @@ static int conv_forward(ConvArgs &a, hipStream_t st)
     const int nb = cfg == 2 ? blocks(64, 128) : cfg == 3 ? blocks(128, 64) : cfg == 5 ? blocks(64, 256) : blocks(128, 32);
     const int Tall = a.kh * a.kw * cv_ncc(a.C);
     int ks = 1;
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-    if (a.nlv == 1 && !a.ostep && nb <= 320 && Tall >= 16) {
-        ks = (512 + nb / 2) / nb;
-        if (ks > Tall / 8) ks = Tall / 8;
-        if (ks > 16) ks = 16;
-        if (ks < 1) ks = 1;
-    }
-#else
     // round 5: stream-K pieces (sk_plan) wherever a tile gets at most four of them, blockIdx.z splits + a reduce launch below
     if (a.nlv == 1 && !a.ostep) ks = z_split(nb, Tall);
-#endif
     switch (cfg) {
     case 2: return launch_conv<1, 2, 2, 2, true>(a, ks, st);
     case 3: return launch_conv<1, 2, 4, 1, false>(a, ks, st);
@@ -437,13 +398,9 @@ int conv_mm_rows(int n, const float *const *x, float *const *out, const int *row
     bool rows32 = true;   // the TRANS epilogue stores through a buffer descriptor of each row block: 32-bit byte offsets
     for (int i = 0; i < n; ++i) rows32 = rows32 && (long long)rows[i] * N * 4 < (1ll << 31) - 256;
     if (N % 256 == 0 && rows32) {   // the 64 x 256 tile with whole-line stores (conv_kernels.h TRANS); plain output, one split
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-        return conv_forward(a, st);
-#else
         return split_dispatch(conv_np(), [&](auto np) {
             return launch_conv_cfg<2, 2, 1, 4, decltype(np)::value, false, true, true>(a, 1, st);
         });
-#endif
     }
     return conv_forward(a, st);
 }
@@ -773,11 +730,7 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     const int blocks = cdiv(a.Co, BM) * cdiv(a.C, BN);
     const size_t nW = (size_t)a.Co * K * a.C;
     const int nj = wg_jobs();   // > 1: the levels are jobs with their own outputs; every split stays inside one level
-#ifdef LSNET_AB_DIST   // build.py --ab -DLSNET_AB_DIST: rounds 3 / 4 work distribution (profiles/r5_sk_*.txt)
-    int S = (512 + blocks * nj / 2) / (blocks * nj);
-#else
     int S = 512 / (blocks * nj);   // one round of workgroups (rounds 3 / 4 rounded to nearest: 516 .. 540 on 512 slots)
-#endif
     const size_t cap = ((size_t)192 << 20) / 4 / (nW + a.Co) / nj;   // partial tiles: at most 192 MB
     if ((size_t)S > cap) S = (int)cap;
     if (S > a.nseg / nj / 6) S = a.nseg / nj / 6;   // a split should run long enough to amortise its prologue and its partial tile
@@ -824,11 +777,7 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
 
 static int reduce_ls(int splits)
 {
-#ifdef LSNET_PER_LANE
-    constexpr int PER_LANE = LSNET_PER_LANE;
-#else
     constexpr int PER_LANE = 16;
-#endif
     int LS = 1;
     while (LS < 64 && LS * PER_LANE <= splits) LS <<= 1;
     return LS;
@@ -877,11 +826,7 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
     // partial tiles a lane sums on its own before the xor-shuffles (LS = splits / PER_LANE lanes share a float4).  Round-4 sweep
     // (tools/ubench/wgrad_ab rule / bn, us per step of the benchmark's layer mix): 4: 3374 / 2945, 8: 3284 / 2729,
     // 16: 3254 / 2650, 32: 3252 / 2642 -- fewer, longer lanes win until the loads in flight run out.
-#ifdef LSNET_PER_LANE
-    constexpr int PER_LANE = LSNET_PER_LANE;
-#else
     constexpr int PER_LANE = 16;
-#endif
     while (LS < 64 && LS * PER_LANE <= splits) LS <<= 1;   // >= PER_LANE / 2 loads per lane; a wave's lanes share 64 / LS elements
     if (g_wg_fold) {
         const int nj = g_wg_fold->njobs;   // (splits / splits_b count ALL jobs' partial tiles)

@@ -29,9 +29,10 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-// optional phase-clock capture (diagnostics only; see lsn_debug_phase_clocks)
+// optional phase-clock capture and kernel routing for tests / A/B runs (diagnostics only; see lsn_debug_phase_clocks)
 static long long *g_dbg_buf = nullptr;
 static int g_dbg_block = 0;
+static bool dbg_on(int bit) { return (g_dbg_block & bit) != 0; }   // bit: one of the LSN_DBG_* of lsnet_hip.h
 
 // arithmetic of the implicit-GEMM contractions: exact fp32 MFMA, or split-bf16 products (common.h)
 static int g_math_mode = -1;   // -1: not initialised (LSNET_MATH decides at first use)
@@ -58,7 +59,6 @@ static int math_np()
     }
 }
 int split_np() { return math_np(); }
-void dbg_state(long long **buf, int *block) { *buf = g_dbg_buf, *block = g_dbg_block; }
 
 // ---- per-kernel launch timing (prof.h) ----
 static const char *const kProfNames[PROF_N] = {"dcn_fwd", "dcn_bwd_data", "dcn_wgrad", "conv_fwd", "conv_bwd_data",
@@ -259,7 +259,7 @@ static bool vec_ok(const DcnArgs &a)
 // ---- the kernels of dcn_mm_kernels.h (dense-convolution skeleton): conditions, weight image, launches ----
 static bool dcn_mm_env()
 {
-    return !((g_dbg_block >> 28) & 1);   // bit 28 of the debug word: the kernels of dcn_kernels.h only (tests, A/B runs)
+    return !dbg_on(LSN_DBG_GENERAL_GEMMS);   // the kernels of dcn_kernels.h only (tests, A/B runs)
 }
 
 static bool mm_common_ok(const DcnArgs &a)
@@ -324,23 +324,22 @@ static int mm_prepare_weights(DcnArgs &a, bool backward, void *dst, hipStream_t 
 
 // Work distribution of a forward launch (dcn_mm_kernels.h DcnSk).  The chip holds 512 workgroups of the kernel; whole rounds
 // stay one workgroup per tile, the r tiles of the last round are cut into pieces of >= 4 chunks spread evenly over up to 512
-// workgroups.  Measured (tools/ubench/dcn_step, debug bit 19 = whole tiles only, profiles/r6_dcn_sk.txt): the pyramid launch
+// workgroups.  Measured (tools/ubench/dcn_step, LSN_DBG_FWD_SK_NEVER = whole tiles only, profiles/r6_dcn_sk.txt): the pyramid launch
 // (2 100 tiles: four rounds and 52 tiles) 780 -> 759 us; the tower launch (700 tiles: one round and 188 tiles) 278 -> 283 us --
 // its second round runs one workgroup per CU, which has the matrix pipe to itself and finishes in ~0.65 of a round, so the
 // even split has little to return and the pieces' table rebuild and hand-over cost more.  Hence: launches of two rounds and
 // more only (the opposite of the dense kernel's rule, conv.hip sk_plan, whose short tiles lose to the longer prologue there).
 int conv_sk_scratch(size_t floats, float **part, unsigned **cnt, hipStream_t st);
 int conv_sk_max_tiles();
-static bool dcn_sk_env() { return !((g_dbg_block >> 19) & 1); }   // debug bit 19: whole tiles only (A/B)
 static void dcn_sk_plan(int ntw, int Tall, DcnSk *sk)
 {
     sk->n_dp = ntw, sk->sk_n = 0, sk->sk_tiles = 0, sk->part = nullptr, sk->cnt = nullptr;
     constexpr int SLOTS = 512;
-    const bool forced = (g_dbg_block >> 18) & 1;   // debug bit 18: pieces for launches of any size (tests)
+    const bool forced = dbg_on(LSN_DBG_FWD_SK_ALWAYS);   // pieces for launches of any size (tests)
     // launches of less than HALF a round (a backbone layer of configs 3 / 4: 8 400 pixels = 132 tiles, 2 100 = 33) leave most
     // of the chip idle as whole tiles: up to four pieces per tile (the dense kernel's rule); between half a round and two
     // rounds (the tower launch) whole tiles win, see above
-    if (!dcn_sk_env() || Tall < 8 || (ntw >= SLOTS / 2 && ntw < 2 * SLOTS && !forced)) return;
+    if (dbg_on(LSN_DBG_FWD_SK_NEVER) || Tall < 8 || (ntw >= SLOTS / 2 && ntw < 2 * SLOTS && !forced)) return;
     const int r = ntw % SLOTS;
     if (r == 0 || r > 448) return;
     int per_tile = Tall / 4;
@@ -413,15 +412,13 @@ static bool xn_ok(const DcnArgs &a)
     if ((int64_t)a.Co * a.kh * a.kw * (a.C / a.groups) * 4 >= (int64_t)1 << 31) return false;
     for (int i = 0; i < a.nlv; ++i)
         if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C * 4 >= (int64_t)1 << 31) return false;
-    return !((g_dbg_block >> 29) & 1);   // bit 29 of the debug word forces the two-workgroup variant (A/B runs)
+    return true;
 }
 
 // ---- grouped calls (dcn_grouped_kernels.h): ResNeXt's 64 groups of 8 / 16 / 32 channels ----
-static bool grouped_env() { return !((g_dbg_block >> 17) & 1); }   // debug bit 17: the general kernels for grouped calls (tests, A/B)
-
 static bool grouped_fwd_ok(const DcnArgs &a)
 {
-    if (a.groups <= 1 || !grouped_env() || a.C % a.groups != 0 || a.Co != a.C) return false;
+    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C) return false;
     const int cg = a.C / a.groups;
     if (!(cg == 8 || cg == 16 || cg == 32) || a.C % GF_CH != 0 || a.C % a.dg != 0 || (a.C / a.dg) % GF_CH != 0) return false;
     if (dcn_fwd_grouped_lds_bytes(a.kh * a.kw) > 64 * 1024) return false;
@@ -514,7 +511,7 @@ static bool bwd_x3_ok(const DcnArgs &a)
 
 static bool bwd_colbuf_env()
 {
-    return !((g_dbg_block >> 23) & 1);   // bit 23 of the debug word forces the atomic scatter kernels (tests)
+    return !dbg_on(LSN_DBG_ATOMIC_SCATTER);   // the atomic scatter kernels (tests)
 }
 
 // Exact-fp32 column gradients (dcn_gcol_grouped_kernel: fmaf chains per group) in front of the gather pass: grouped calls
@@ -668,10 +665,10 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl)
     pl.o_S = o, o = align256(o + (size_t)pl.aa.NA * 4 * a.C * sizeof(float));
     // corner sums (dcn_offgrad_kernel): one slot per 256-channel block where the per-anchor sums split them over blockIdx.y
     // (every group on the per-anchor path, C > 256; dcn_gather_kernels.h AnchorArgs::ncb)
-    // (debug bit 16: one wave walks all blocks of its anchor, the form until round 6 -- A/B runs; the workspace is sized for
+    // (LSN_DBG_ANCHOR_ONE_WAVE: one wave walks all blocks of its anchor, the form until round 6 -- tests; the workspace is sized for
     // the split either way, so a size asked for under one setting serves a launch under the other)
     const int ncb_max = (ga.NB == 0 && aa.ng > 0 && a.C > 256) ? cdiv(a.C, 256) : 1;
-    aa.ncb = ((g_dbg_block >> 16) & 1) ? 1 : ncb_max;
+    aa.ncb = dbg_on(LSN_DBG_ANCHOR_ONE_WAVE) ? 1 : ncb_max;
     aa.hb_slot = (long long)pl.nsamples * 4;
     pl.o_H = o, o = align256(o + (size_t)pl.nsamples * 4 * sizeof(float) * ncb_max);
     pl.o_ent2 = o, o = align256(o + (size_t)pl.nsamples * sizeof(GEntry));   // ordering of the lists above 64 entries
@@ -735,7 +732,6 @@ static int side_stream(hipStream_t st, SideStream **out)
     *out = &S;
     return 0;
 }
-static bool side_lists_env() { return !((g_dbg_block >> 21) & 1); }   // debug bit 21: lists on the launch stream (A/B)
 
 // (Round 5 cut the launch into bands -- an anchor range per image of a grad_input map + the GEMM rows that scatter into it --
 // and ran the per-anchor sums of band i on the side stream beside the GEMM of band i + 1, the column gradients of a band
@@ -753,7 +749,7 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
     a.gtap_rows = pl.nsamples / (a.kh * a.kw * a.dg);
     // lists on the side stream only beside the dense GEMM (the other column-gradient kernels read the tap table)
     SideStream *side = nullptr;
-    if (a.mm && a.groups == 1 && side_lists_env())
+    if (a.mm && a.groups == 1)
         if (int rc = side_stream(st_main, &side)) return rc;
     hipStream_t st = side ? side->side : st_main;
     if (side) {
@@ -781,7 +777,7 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
     if (grouped) {   // exact-fp32 column gradients per group, unweighted; the gather pass does the rest as for the dense GEMM
         int ks = 0;   // k-steps of the fp32-MFMA form (dcn_grouped_kernels.h dcn_gcol_mfma_kernel); 0: the fmaf-chain kernel
         const int Cg = a.C / a.groups, Cog = a.Co / a.groups;
-        if (grouped_env() && a.C % GC_COLS == 0 && a.opitch % 4 == 0) {
+        if (a.C % GC_COLS == 0 && a.opitch % 4 == 0) {
             if (a.groups == 1 && (a.Co == 64 || a.Co == 128 || a.Co == 256)) ks = a.Co / 4;
             if (a.groups > 1 && Cog == Cg && (Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32)) ks = Cg == 32 ? 8 : 4;
             for (int i = 0; i < a.nlv; ++i)
@@ -1012,7 +1008,7 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
 
 static bool grouped_wgrad_ok(const DcnArgs &a)
 {
-    if (a.groups <= 1 || !grouped_env() || a.C % a.groups != 0 || a.Co != a.C || a.kh * a.kw > 9) return false;
+    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C || a.kh * a.kw > 9) return false;
     const int cg = a.C / a.groups;
     if (!(cg == 4 || cg == 8 || cg == 16 || cg == 32) || ((int64_t)a.C * cg) % 256 != 0 || a.C % a.dg != 0) return false;
     const int nch = cg >= 16 ? cg : 256 / cg;
@@ -1098,8 +1094,7 @@ static int launch_wgrad(const DcnArgs &a_in, int nsteps, bool accumulate, hipStr
     // split-bf16 kernels: one partial gradient per pixel split + an ordered reduce instead of fp32 atomics (deterministic);
     // a block that runs no step still stores its zero tile, so every partial element is written
     const size_t nW = (size_t)a.Co * K * Cg;
-    const bool ordered = !((g_dbg_block >> 30) & 1) && nW % 4 == 0 &&
-                         (size_t)splits * (nW + a.Co) * sizeof(float) <= ((size_t)256 << 20);
+    const bool ordered = nW % 4 == 0 && (size_t)splits * (nW + a.Co) * sizeof(float) <= ((size_t)256 << 20);
     if (ordered) {
         float *base = nullptr;
         if (int rc = conv_scratch((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
@@ -1130,8 +1125,7 @@ static int launch_wgrad(const DcnArgs &a_in, int nsteps, bool accumulate, hipStr
         if (int rc = split_dispatch(math_np(), go_xn)) return rc;
         return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
     }
-    if (math_np() && !((g_dbg_block >> 30) & 1))   // bit 30: force the fp32 MFMA kernel
-        return split_dispatch(math_np(), go_xn);
+    if (math_np()) return split_dispatch(math_np(), go_xn);
     if (vec_ok(a))
         hipLaunchKernelGGL(dcn_wgrad_kernel<true>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
     else
@@ -1396,10 +1390,6 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
 int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
                   int dil, int accumulate, hipStream_t st);   // conv.hip
 
-// bits 26 / 27 of the debug word (tools/ubench/wgrad_ab: A/B runs): 0 never, 1 every shape the kernel serves; default (2):
-// the shapes it won on (conv_wgrad_dense_mm)
-static int conv_wgrad_mm_env() { return ((g_dbg_block >> 26) & 1) ? 0 : ((g_dbg_block >> 27) & 1) ? 1 : 2; }
-
 // The weight gradient of a dense convolution through dcn_wgrad_mm_kernel<NP, DENSE> (grad_output pre-split once into MFMA
 // fragment order, the regular grid as the sampling table).  Returns 1 when the shape is not served (256 | Co, 64 | C,
 // 32-bit byte offsets, a split-bf16 math mode) or is faster on the patch kernel of conv_wgrad_kernels.h.  Measured on the
@@ -1410,17 +1400,15 @@ static int conv_wgrad_mm_env() { return ((g_dbg_block >> 26) & 1) ? 0 : ((g_dbg_
 static int conv_wgrad_dense_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
                                int pad, int dil, bool accumulate, hipStream_t st)
 {
-    if (!conv_wgrad_mm_env() || n < 1 || n > MAXLV || !lv || !gw || Co % 256 != 0 || C % 64 != 0) return 1;
-    if (conv_wgrad_mm_env() != 1) {
-        int64_t px = 0;
-        for (int i = 0; i < n; ++i) {
-            const int Ho = (lv[i].H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (lv[i].W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
-            px += (int64_t)lv[i].B * (Ho > 0 ? Ho : 0) * (Wo > 0 ? Wo : 0);
-        }
-        // (all of them measured at >= 2100 output pixels; smaller launches stay where they were)
-        const bool win = kh * kw >= 9 ? px >= 4096 : px >= 2048 && ((C >= 1024 && Co >= 512) || (stride >= 2 && C >= 512));
-        if (!win) return 1;
+    if (n < 1 || n > MAXLV || !lv || !gw || Co % 256 != 0 || C % 64 != 0) return 1;
+    int64_t opx = 0;   // output pixels
+    for (int i = 0; i < n; ++i) {
+        const int Ho = (lv[i].H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (lv[i].W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
+        opx += (int64_t)lv[i].B * (Ho > 0 ? Ho : 0) * (Wo > 0 ? Wo : 0);
     }
+    // (all of them measured at >= 2100 output pixels; smaller launches stay where they were)
+    const bool win = kh * kw >= 9 ? opx >= 4096 : opx >= 2048 && ((C >= 1024 && Co >= 512) || (stride >= 2 && C >= 512));
+    if (!win) return 1;
     DcnArgs a = {};
     int chunks = 0;
     for (int i = 0; i < n; ++i) {
@@ -1502,10 +1490,13 @@ extern "C" {
 
 const char *lsn_last_error(void) { return lsn::err_buf(); }
 
-int lsn_debug_phase_clocks(long long *device_buf_512, int block)
+int lsn_debug_phase_clocks(long long *device_buf_512, int word)
 {
+    constexpr int known = LSN_DBG_BLOCK_MASK | LSN_DBG_ANCHOR_ONE_WAVE | LSN_DBG_FWD_SK_ALWAYS | LSN_DBG_FWD_SK_NEVER |
+                          LSN_DBG_ATOMIC_SCATTER | LSN_DBG_WG_COMPUTED_TAPS | LSN_DBG_WG_SCALAR_LOADS | LSN_DBG_GENERAL_GEMMS;
+    if (word & ~known) return fail(LSN_ERR_INVALID, "lsn_debug_phase_clocks: unknown debug bits 0x%x", (unsigned)(word & ~known));
     lsn::g_dbg_buf = device_buf_512;
-    lsn::g_dbg_block = block;
+    lsn::g_dbg_block = word;
     return 0;
 }
 int lsn_version(void) { return 100; }

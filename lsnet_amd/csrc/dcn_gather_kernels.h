@@ -179,31 +179,6 @@ __global__ void dcn_bin_kernel(const DcnArgs a, int nsamples, int *__restrict__ 
     sfrac[s] = fr;
 }
 
-// exclusive prefix sum of cnt[0..n) into start[0..n], one workgroup of 1024 threads
-__global__ __launch_bounds__(1024) void dcn_scan_kernel(const int *__restrict__ cnt, int *__restrict__ start, int n)
-{
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int b = min(tid * per, n), e = min(b + per, n);
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += cnt[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {   // Hillis-Steele inclusive scan
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-    for (int i = b; i < e; ++i) {
-        start[i] = run;
-        run += cnt[i];
-    }
-    if (tid == 1023) start[n] = part[1023];
-}
-
 __global__ void dcn_fill_kernel(int nsamples, const int *__restrict__ start, const int *__restrict__ sanchor,
                                 const int *__restrict__ srank, const float2 *__restrict__ sfrac, GEntry *__restrict__ ent,
                                 const Tap *__restrict__ gtap, int KD, int gtap_rows)

@@ -813,9 +813,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_data_kernel(const DcnArgs a)
     const int segs = Cg / a.SL, ncc = (a.SL + BK - 1) / BK;
     const int T = K * segs * ncc;
     const int nrb = (Cog + RED - 1) / RED;  // reduction blocks (1 for Co/groups <= RED)
-    // bits 26..28 of the debug word: timing ablations (tools/phase_clocks.py bwd); results are wrong when set
-    const bool abl_no_atomic = (a.dbg_block >> 26) & 1;
-    const bool want_off = ((L.goff != nullptr) || (L.gmsk != nullptr)) && !((a.dbg_block >> 27) & 1);
+    const bool want_off = (L.goff != nullptr) || (L.gmsk != nullptr);
 
     const int wq = tid & 7, wrow = tid >> 3;  // weight staging: float4 slot along k, 32 rows/pass
     constexpr int NPB = RED / 32;
@@ -925,7 +923,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_data_kernel(const DcnArgs a)
                     float b00, b01, b10, b11;
                     corner_weights(tp, b00, b01, b10, b11);
                     const float gm = gval * tp.m;
-                    if (L.gx != nullptr && cval && tp.flags && !abl_no_atomic) {
+                    if (L.gx != nullptr && cval && tp.flags) {
                         // one guard per sample, not per corner: a clamped corner of a border sample gets +0 at
                         // a valid neighbour address (wholly invalid samples must be skipped: their index is 0
                         // and thousands of same-address atomics serialise in L2)
@@ -1575,8 +1573,9 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_xn_kernel(const DcnArgs a, i
     // 8-byte buffer loads need even channel counts and bases, 8-byte aligned tensors and byte offsets below 2^31
     // (tensor alignment and sizes: checked by the host, a.wg_vec bit 0 = input, bit 1 = grad_output)
     bool vx = (a.wg_vec & 1) && (cbase & 1) == 0, vg = (a.wg_vec & 2) && (co_base & 1) == 0;
-    if ((a.dbg_block >> 25) & 1) vx = vg = false;   // diagnostic: scalar loads
+    if ((a.dbg_block >> 25) & 1) vx = vg = false;   // diagnostic: scalar loads (LSN_DBG_WG_SCALAR_LOADS)
     // the backward-data pass of the same call left the sampling table of every (pixel, tap) in a.gtap (k-major)
+    // (bit 24: LSN_DBG_WG_COMPUTED_TAPS)
     const bool use_gtap = !PLAIN && vx && vg && a.gtap != nullptr && !((a.dbg_block >> 24) & 1);
 
     constexpr int NX = PLAIN ? 1 : 4;
@@ -1741,47 +1740,6 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_xn_kernel(const DcnArgs a, i
         }
     };
 
-#ifdef LSN_WG_INTERLEAVE
-    // Experiment (not the default build): the 8-byte loads of step st + 1 issued one by one in the gaps between the MFMAs
-    // of step st instead of as a block before them (the block costs ~2.5 k cycles of pure issue time per step).
-    constexpr int IL_NL = 4 * NX + WG_BP / 2, IL_NG = 2 * NP * TI * TI;
-    int il_xoff[4][NX];
-    int il_g0 = 0, il_rowb = 0, il_xbytes = 0, il_gbytes = 0;
-    const float *il_xp = nullptr, *il_gp = nullptr;
-    auto il_prepare = [&](int st, int buf) __attribute__((always_inline)) {
-        const Lvl &L = find_level(a, st);
-        const int p0 = (st - L.tile0) * WG_BP;
-        il_xp = L.x, il_gp = L.gout;
-        il_xbytes = L.B * L.H * L.W * a.C * 4, il_gbytes = L.P * a.Co * 4;
-        const int c4 = (cbase + 2 * kp) * 4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const Tap *tp = &tab[buf * WG_BP + pg * 4 + q];
-            if (PLAIN) {
-                il_xoff[q][0] = tp->i00 * 4 + c4;
-            } else {
-                const int4 i4 = *reinterpret_cast<const int4 *>(tp);
-                il_xoff[q][0] = i4.x * 4 + c4, il_xoff[q][NX > 1 ? 1 : 0] = i4.y * 4 + c4;
-                il_xoff[q][NX > 2 ? 2 : 0] = i4.z * 4 + c4, il_xoff[q][NX > 3 ? 3 : 0] = i4.w * 4 + c4;
-            }
-        }
-        il_g0 = ((p0 + gph * (WG_BP / 2)) * a.Co + co_base + 2 * gcp) * 4;
-        il_rowb = a.Co * 4;
-    };
-    auto il_issue = [&](int m) __attribute__((always_inline)) {
-        if (m < 4 * NX) {
-            const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(il_xp), 0, il_xbytes, 0x00020000);
-            const int q = m / NX, e = m - q * NX;
-            const float2 v = buf_load_f32x2(xrs, il_xoff[q][e], 0);
-            xv0[q][e] = v.x, xv1[q][e] = v.y;
-        } else if (gact) {
-            const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(il_gp), 0, il_gbytes, 0x00020000);
-            const int px = m - 4 * NX;
-            const float2 v = buf_load_f32x2(grs, il_g0 + px * il_rowb, 0);
-            gv0[px] = v.x, gv1[px] = v.y;
-        }
-    };
-#endif
     int dbg_n = 0;
     // Tap-table slots rotate over three steps: slot (i % 3) holds step st_begin + i.  Iteration st stages step st,
     // issues the loads of step st + 1 (indices from slot st + 1) and, after its MFMA block, fills slot st + 2:
@@ -1790,30 +1748,6 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_xn_kernel(const DcnArgs a, i
     //   !GT (computed): the entry's offset / mask loads are issued before the MFMA block and finished after it.
     // (GT: the table load is issued by every wave, unconditionally and always as the YOUNGEST load in flight, also in
     // the prologue: only then can the compiler count on it and let the staging code wait with vmcnt(1) instead of 0.)
-#ifdef LSN_WG_INTERLEAVE
-#define LSN_WG_LOADS(st, slot1, VXT, VGT)                                                                             \
-    do {                                                                                                              \
-        if constexpr (VXT::value && VGT::value) il_prepare(min(st + 1, st_end - 1), (st + 1 < st_end) ? slot1 : slot); \
-        else if (st + 1 < st_end) load_step(st + 1, slot1, VXT{}, VGT{});                                             \
-    } while (0)
-#define LSN_WG_GAP(gap, VXT, VGT)                                                                                     \
-    do {                                                                                                              \
-        if constexpr (VXT::value && VGT::value) {                                                                     \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-_Pragma("unroll")                                                                                                     \
-            for (int m_ = (gap) * IL_NL / IL_NG; m_ < ((gap) + 1) * IL_NL / IL_NG; ++m_) il_issue(m_);                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-        }                                                                                                             \
-    } while (0)
-#else
-#define LSN_WG_LOADS(st, slot1, VXT, VGT)                                                                             \
-    do {                                                                                                              \
-        if (st + 1 < st_end) load_step(st + 1, slot1, VXT{}, VGT{});                                                  \
-    } while (0)
-#define LSN_WG_GAP(gap, VXT, VGT)                                                                                     \
-    do {                                                                                                              \
-    } while (0)
-#endif
 #define LSN_WG_RUN(VXT, VGT, GTB)                                                                                     \
     do {                                                                                                              \
         uint4 tq = make_uint4(0u, 0u, 0u, 0u);                                                                        \
@@ -1841,7 +1775,7 @@ _Pragma("unroll")                                                               
             const bool build2 = !(GTB) && st + 2 < st_end && tid < WG_BP;                                             \
             Tap t2 = {};                                                                                              \
             if (build2) t2 = tap_of(st + 2);                                                                          \
-            LSN_WG_LOADS(st, slot1, VXT, VGT);                                                                        \
+            if (st + 1 < st_end) load_step(st + 1, slot1, VXT{}, VGT{});                                              \
             LSN_STAMP(5);                                                                                             \
             const unsigned char *ap = smem + (row0 + (lane & 31)) * RS + (lane >> 5) * 16;                            \
             const unsigned char *bp = smem + NPL * PLANE_A + (col0 + (lane & 31)) * RS + (lane >> 5) * 16;            \
@@ -1861,10 +1795,7 @@ _Pragma("unroll")                                                               
                     for (int i = 0; i < TI; ++i)                                                                      \
 _Pragma("unroll")                                                                                                     \
                         for (int j = 0; j < TI; ++j)                                                                  \
-                        {                                                                                             \
                             acc[i][j] = mfma_bf16(Af[i][SC::pa(prod)], Bf[j][SC::pb(prod)], acc[i][j]);               \
-                            LSN_WG_GAP(((ks * NP + prod) * TI + i) * TI + j, VXT, VGT);                               \
-                        }                                                                                             \
             }                                                                                                         \
             LSN_STAMP(6);                                                                                             \
             if constexpr (GTB) {                                                                                      \
@@ -1892,8 +1823,6 @@ _Pragma("unroll")                                                               
         }
     }
 #undef LSN_WG_RUN
-#undef LSN_WG_LOADS
-#undef LSN_WG_GAP
 
     // every element of the gradient belongs to exactly one (column block, co block): with a partial buffer per pixel
     // split the epilogue is a plain store and the splits are added in a fixed order afterwards

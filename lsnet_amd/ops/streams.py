@@ -17,8 +17,7 @@ Rules for whoever puts work on this stream:
     stream only behind `main.wait_stream(side)`, and their memory returns to the pool when the next side-stream block starts with
     `wait_stream(main)` again (LSHead.forward_train) -- no `record_stream` needed under this rule, and a block that begins with
     `wait_event` must not allocate at all (the rebuild writes into long-lived image buffers);
-  * main-stream tensors READ on the side stream while the main stream runs on are protected with `record_stream`
-    (ops/resblock.py `_on_side`)."""
+  * main-stream tensors READ on the side stream while the main stream runs on are protected with `record_stream`."""
 import os
 
 import torch

@@ -50,6 +50,49 @@ def test_argument_checks_need_no_gpu(built_lib):
         _lib.check(rc)
 
 
+def _debug_bits():
+    """{name: value} of the LSN_DBG_* enum of include/lsnet_hip.h, without the prefix LSN_"""
+    text = open(os.path.join(ROOT, 'include', 'lsnet_hip.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    bits = {}
+    for name, value in re.findall(r'\bLSN_(DBG_[A-Z0-9_]+)\s*=\s*([^,}]+)', text):
+        shift = re.fullmatch(r'1\s*<<\s*(\d+)', value.strip())
+        bits[name] = 1 << int(shift.group(1)) if shift else int(value, 0)
+    return bits
+
+
+def test_debug_word_constants_match_header():
+    from lsnet_amd import _lib
+    bits = _debug_bits()
+    assert len(bits) == 8 and bits['DBG_BLOCK_MASK'] == 0xffff
+    for name, value in bits.items():
+        assert getattr(_lib, name) == value, name
+
+
+def test_debug_word_refuses_unknown_bits(built_lib):
+    """lsn_debug_phase_clocks takes a workgroup index and the named routing bits.  Any other bit is refused: the bits of
+    finished experiments (17, 26, 27, 29, 30), the old places of the moved ones (16, 18, 19) and bits that never meant
+    anything.  The _lib setter raises for the same words."""
+    from lsnet_amd import _lib
+    lib = _lib.load()
+    bits = _debug_bits()
+    named = [v for k, v in bits.items() if k != 'DBG_BLOCK_MASK']
+    known = bits['DBG_BLOCK_MASK'] | sum(named)
+    unknown = [1 << b for b in range(32) if not (known >> b) & 1]
+    assert {1 << b for b in (16, 17, 18, 19, 26, 27, 29, 30, 31)} == set(unknown)
+    try:
+        for word in unknown + [(1 << 26) | 5, (1 << 27) | _lib.DBG_GENERAL_GEMMS]:
+            assert lib.lsn_debug_phase_clocks(None, ctypes.c_int(word)) == -1, hex(word)
+            assert b'unknown debug bits' in lib.lsn_last_error()
+            with pytest.raises(RuntimeError, match='unknown debug bits'):
+                _lib.set_debug_word(word)
+        for word in [0, 300, bits['DBG_BLOCK_MASK']] + named + [sum(named) | 17]:
+            assert lib.lsn_debug_phase_clocks(None, ctypes.c_int(word)) == 0, hex(word)
+            _lib.set_debug_word(word)
+    finally:
+        _lib.set_debug_word(0)
+
+
 def test_product_ops_refuse_cpu_tensors():
     """No CPU fallback in the product: like the reference (deform_conv.py:46-47) CPU tensors raise in the device-only ops."""
     import torch

@@ -31,7 +31,7 @@ def math_mode():
     before = _lib.get_math_mode()
     yield _lib.set_math_mode
     _lib.set_math_mode(before)
-    _lib.load().lsn_debug_phase_clocks(None, 0)
+    _lib.set_debug_word(0)
 
 
 # measured on the MI355X (bf16 against fp64 of the rounded operands, fraction of the output range): <= 2.9e-7 over the
@@ -155,13 +155,13 @@ def test_dcn_bf16(case, layout, routing, math_mode):
     differ in the last bits) and is held to 1e-4.  The wide single-group layers must run their contractions in bf16.  The
     forward, where it ran in bf16, equals the rounded-column evaluation to 1e-4 of its range but for isolated samples whose
     blended value lies at a bf16 rounding midpoint (the kernel's fp32 blend and the reference's differ in the last bit, so
-    the two round apart by one bf16 step).  routing 'first_gemms': debug bit 28, the GEMMs of dcn_kernels.h where
+    the two round apart by one bf16 step).  routing 'first_gemms': DBG_GENERAL_GEMMS, the GEMMs of dcn_kernels.h where
     dcn_mm_kernels.h would serve."""
     from lsnet_amd import _lib, ops
     dev = _dev()
     x, w, b, off, mask, go, cfg = _make(case, dev, seed=11)
     truth = _truth(case, dev)
-    _lib.load().lsn_debug_phase_clocks(None, (1 << 28) if routing == 'first_gemms' else 0)
+    _lib.set_debug_word(_lib.DBG_GENERAL_GEMMS if routing == 'first_gemms' else 0)
     cl = layout == 'nhwc'
     math_mode('bf16x6')
     x6 = _dcn_all(ops, x, w, b, off, mask, go, cfg, dev, cl)

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import oracle_py as orc  # noqa: E402  (the checker)
+from lsnet_amd import _lib  # noqa: E402
 
 TOL = 1e-4
 
@@ -128,14 +129,15 @@ def _to(t, dev, cl):
 
 
 KERNEL_CHOICES = {
-    # name: (math mode, debug word).  Bit 23: atomic scatter instead of the anchor-list gather (lsn_debug_phase_clocks).  The split
-    # weight-gradient kernel reads bits 24 / 25 as "compute the sampling table instead of copying the launch-wide one" / "scalar
-    # loads": the one atomic choice below also covers those fallback paths.  (Round 6: the windowed scatter kernels and the
-    # pipelined fp32 forward are gone, 7 -> 5 choices; the exact mode takes the atomic-free gather as well.)
+    # name: (math mode, debug word of lsn_debug_phase_clocks).  DBG_ATOMIC_SCATTER: atomic scatter instead of the anchor-list
+    # gather.  The split weight-gradient kernel reads DBG_WG_COMPUTED_TAPS / DBG_WG_SCALAR_LOADS as "compute the sampling table
+    # instead of copying the launch-wide one" / "scalar loads": the one atomic choice below also covers those fallback paths.
+    # (Round 6: the windowed scatter kernels and the pipelined fp32 forward are gone, 7 -> 5 choices; the exact mode takes the
+    # atomic-free gather as well.)
     'default': ('bf16x6', 0),                       # fp32-equivalent products, atomic-free grad_input
-    'x6_first_gemms': ('bf16x6', 1 << 28),          # bit 28: dcn_kernels.h GEMMs where dcn_mm_kernels.h would serve
+    'x6_first_gemms': ('bf16x6', _lib.DBG_GENERAL_GEMMS),   # dcn_kernels.h GEMMs where dcn_mm_kernels.h would serve
     'x3_gather': ('bf16x3', 0),
-    'x3_atomic_fallbacks': ('bf16x3', (1 << 23) | (1 << 24) | (1 << 25)),
+    'x3_atomic_fallbacks': ('bf16x3', _lib.DBG_ATOMIC_SCATTER | _lib.DBG_WG_COMPUTED_TAPS | _lib.DBG_WG_SCALAR_LOADS),
     'math_fp32': ('fp32', 0),                       # exact fp32: fp32 MFMA forward / weight gradient, fmaf column gradients + gather
 }
 
@@ -146,12 +148,12 @@ def dcn_kernel_choice(request):
     mode and with exact fp32 MFMA everywhere."""
     from lsnet_amd import _lib
     mode, flag = KERNEL_CHOICES[request.param]
-    _lib.load().lsn_debug_phase_clocks(None, flag)
+    _lib.set_debug_word(flag)
     old = _lib.get_math_mode()
     _lib.set_math_mode(mode)
     yield request.param
     _lib.set_math_mode(old)
-    _lib.load().lsn_debug_phase_clocks(None, 0)
+    _lib.set_debug_word(0)
 
 
 @pytest.mark.parametrize('layout', ['nchw', 'nhwc'])
@@ -1136,7 +1138,7 @@ def test_tower_launch_at_bench_shape(choice):
     msks = [torch.rand(2, 9, h, ww, generator=g) for h, ww in FPN_SIZES]
     gos = [torch.randn(2, Co, h, ww, generator=g) for h, ww in FPN_SIZES]
     old = _lib.get_math_mode()
-    _lib.load().lsn_debug_phase_clocks(None, flag)
+    _lib.set_debug_word(flag)
     _lib.set_math_mode(mode)
     try:
         wd, bd = _to(w, dev, True).requires_grad_(), b.to(dev).requires_grad_()
@@ -1155,7 +1157,7 @@ def test_tower_launch_at_bench_shape(choice):
                 assert torch.equal(g1, g2), f'tensor {k} of the data-side gradients differs between two runs'
     finally:
         _lib.set_math_mode(old)
-        _lib.load().lsn_debug_phase_clocks(None, 0)
+        _lib.set_debug_word(0)
     gw_ref, gb_ref = torch.zeros_like(w), torch.zeros_like(b)
     errs = {}
     for i in range(5):
@@ -1177,8 +1179,8 @@ def test_tower_launch_at_bench_shape(choice):
                          ids=['3lv', '4lv_one_round_and_more', 'one_tile_row'])
 def test_dcn_forward_stream_k_pieces(sizes):
     """Round 6: the deformable forward's stream-K pieces (dcn_mm_kernels.h DcnSk; production: launches of two rounds of workgroups
-    and more, i.e. the 15-pair pyramid launch -- test_pyramid_launch_at_bench_shape runs that one against the oracle).  Debug bit
-    18 asks for pieces at any size: the result must equal the oracle's, agree with the whole-tile launch up to the summation order of
+    and more, i.e. the 15-pair pyramid launch -- test_pyramid_launch_at_bench_shape runs that one against the oracle).
+    DBG_FWD_SK_ALWAYS asks for pieces at any size: the result must equal the oracle's, agree with the whole-tile launch up to the summation order of
     the pieces, and come out bit for bit the same on every run (the tile's last arriver adds the slots in chunk order)."""
     from lsnet_amd import _lib, ops
     dev = _dev()
@@ -1193,16 +1195,16 @@ def test_dcn_forward_stream_k_pieces(sizes):
     xd, od, md = [_to(t, dev, True) for t in xs], [_to(t, dev, True) for t in offs], [_to(t, dev, True) for t in msks]
 
     def run(flag):
-        _lib.load().lsn_debug_phase_clocks(None, flag)
+        _lib.set_debug_word(flag)
         try:
             with torch.no_grad():
                 return [o.clone() for o in ops.dcn_multi(xd, od, md, wd, bd, 1, 1, 1)]
         finally:
-            _lib.load().lsn_debug_phase_clocks(None, 0)
+            _lib.set_debug_word(0)
 
-    whole = run(1 << 19)
-    pieces = run(1 << 18)
-    again = run(1 << 18)
+    whole = run(_lib.DBG_FWD_SK_NEVER)
+    pieces = run(_lib.DBG_FWD_SK_ALWAYS)
+    again = run(_lib.DBG_FWD_SK_ALWAYS)
     for i in range(len(sizes)):
         ref = orc.deform_conv_forward(xs[i], w, b, offs[i], msks[i], 1, 1, 1)
         assert _report(f'sk/out{i}', pieces[i], ref) < TOL
@@ -1317,7 +1319,7 @@ def test_pyramid_launch_at_bench_shape(choice):
         gos.append(torch.randn(2, Co, h, ww, generator=g))
         scales.append(sc)
     old = _lib.get_math_mode()
-    _lib.load().lsn_debug_phase_clocks(None, flag)
+    _lib.set_debug_word(flag)
     _lib.set_math_mode(mode)
     try:
         wd = _to(w, dev, True).requires_grad_()
@@ -1328,7 +1330,7 @@ def test_pyramid_launch_at_bench_shape(choice):
         torch.cuda.synchronize()
     finally:
         _lib.set_math_mode(old)
-        _lib.load().lsn_debug_phase_clocks(None, 0)
+        _lib.set_debug_word(0)
     gw_ref = torch.zeros_like(w)
     gx_ref = [torch.zeros_like(f) for f in feats]
     errs = {}
@@ -1385,7 +1387,7 @@ def test_grouped_backward_is_deterministic(mode):
 def test_anchor_sums_by_channel_block_give_the_same_bits():
     """Round 6: for layers of more than 256 channels the per-anchor sums of the backward-data pass put the 256-channel blocks
     on blockIdx.y (dcn_gather_kernels.h AnchorArgs::ncb) and dcn_offgrad_kernel adds the blocks' corner dot products in block
-    order -- the order in which one wave used to accumulate them (debug bit 16): grad_input, grad_offset and grad_mask are
+    order -- the order in which one wave used to accumulate them (DBG_ANCHOR_ONE_WAVE): grad_input, grad_offset and grad_mask are
     bitwise the same in both forms."""
     from lsnet_amd import _lib, ops
     dev = _dev()
@@ -1393,10 +1395,10 @@ def test_anchor_sums_by_channel_block_give_the_same_bits():
     x, w, b, off, mask, go, cfg = _make(case, dev, seed=6)
     try:
         a = _dcn_all(ops, x, w, b, off, mask, go, cfg, dev)
-        _lib.load().lsn_debug_phase_clocks(None, 1 << 16)
+        _lib.set_debug_word(_lib.DBG_ANCHOR_ONE_WAVE)
         c = _dcn_all(ops, x, w, b, off, mask, go, cfg, dev)
     finally:
-        _lib.load().lsn_debug_phase_clocks(None, 0)
+        _lib.set_debug_word(0)
     for k in ('gx', 'goff', 'gmask'):
         assert torch.equal(a[k], c[k]), k
 

@@ -11,5 +11,5 @@ b = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(b)
 for arg in sys.argv[1:]:
     name, _, defs = arg.partition(':')
-    defines = ['LSNET_AB=1'] + [d[2:] for d in defs.split(',') if d.startswith('-D')]
+    defines = [d[2:] for d in defs.split(',') if d.startswith('-D')]
     print(b.build(force=False, verbose=False, defines=defines, so=os.path.join(b.HERE, 'ab_%s.so' % name)))

@@ -1,5 +1,5 @@
 """Per-chunk cycle anatomy of the DCN forward / backward-data kernels (lsn_debug_phase_clocks)."""
-import sys, os, ctypes
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lsnet_amd import _lib
@@ -11,7 +11,6 @@ LEVELS = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
 B, C = 2, 256
 torch.manual_seed(0)
 be = get_backend(torch.zeros(1, device=dev))
-lib = _lib.load()
 w = (torch.randn(C, C, 3, 3, device=dev) * 0.02).contiguous(memory_format=cl)
 xs = [torch.randn(B, C, h, ww, device=dev).contiguous(memory_format=cl) for h, ww in LEVELS]
 offs = [(torch.randn(B, 18, h, ww, device=dev) * 0.5).contiguous(memory_format=cl) for h, ww in LEVELS]
@@ -27,13 +26,13 @@ def run(fn, block, label, flags=0):
     buf = torch.zeros(512, dtype=torch.int64, device=dev)
     for _ in range(3):
         fn()
-    lib.lsn_debug_phase_clocks(None, flags)
+    _lib.set_debug_word(flags)
     for _ in range(2):
         fn()
-    lib.lsn_debug_phase_clocks(ctypes.c_void_p(buf.data_ptr()), block | flags)
+    _lib.set_debug_word(block | flags, buf.data_ptr())
     fn()
     torch.cuda.synchronize()
-    lib.lsn_debug_phase_clocks(None, 0)
+    _lib.set_debug_word(0)
     v = buf.cpu().tolist()
     st = [(x >> 56, x & ((1 << 56) - 1)) for x in v if x != 0]
     print(f'--- {label}, block {block}: {len(st)} stamps')
@@ -67,10 +66,11 @@ elif len(sys.argv) > 1 and sys.argv[1] == 'conv':
             run(lambda: conv2d(xc, wc, None, 1, k // 2), 17, 'conv forward ' + name)
 elif len(sys.argv) > 1 and sys.argv[1] == 'wgab':
     # weight gradient inside a full backward call (the backward-data pass leaves its sampling table for it):
-    # bit 24 = ignore that table, bit 25 = scalar loads
+    # DBG_WG_COMPUTED_TAPS = ignore that table, DBG_WG_SCALAR_LOADS = scalar loads
     need_all = dict(input=[True] * 5, offset=[True] * 5, mask=[True] * 5, weight=True, bias=True)
-    for name, fl in (('table + 8-byte loads', 0), ('computed taps', 1 << 24), ('scalar loads', 1 << 25)):
-        lib.lsn_debug_phase_clocks(None, fl)
+    for name, fl in (('table + 8-byte loads', 0), ('computed taps', _lib.DBG_WG_COMPUTED_TAPS),
+                     ('scalar loads', _lib.DBG_WG_SCALAR_LOADS)):
+        _lib.set_debug_word(fl)
         for _ in range(3):
             be.dcn_backward(xs, offs, msks, w, gos, cfg, need_all)
         _lib.prof_enable(True)
@@ -79,20 +79,13 @@ elif len(sys.argv) > 1 and sys.argv[1] == 'wgab':
         torch.cuda.synchronize()
         pr = _lib.prof_read()
         _lib.prof_enable(False)
-        lib.lsn_debug_phase_clocks(None, 0)
+        _lib.set_debug_word(0)
         print(f'== {name}: ' + ', '.join(f"{k} {v['total_ms'] / max(v['launches'], 1):.3f} ms" for k, v in pr.items()))
         run(lambda: be.dcn_backward(xs, offs, msks, w, gos, cfg, need_all), 17, 'weight gradient, ' + name, fl)
 elif len(sys.argv) > 1 and sys.argv[1] == 'bwd1':
     # split kernels: 2 loop top, 4 slab landed (barrier), 5 MFMAs done, 3 barrier + next slab issued, 6 epilogue done
     for blk in (0, 300, 600):
         run(lambda: be.dcn_backward(xs, offs, msks, w, gos, cfg, need), blk, 'backward-data (split kernel)')
-elif len(sys.argv) > 1 and sys.argv[1] == 'bwd':
-    for name, fl in (('full', 0), ('no atomics', 1 << 26), ('no offset/mask grads', 1 << 27),
-                     ('neither atomics nor offset grads', 3 << 26)):
-        run(lambda: be.dcn_backward(xs, offs, msks, w, gos, cfg, need), 300, f'backward-data {name}', fl)
-elif len(sys.argv) > 1 and sys.argv[1] == 'ablate':
-    for name, fl in (('full', 0), ('no issue', 2 << 20), ('no issue, commit VALU only', 6 << 20), ('no issue, commit LDS only', 10 << 20)):
-        run(lambda: be.dcn_forward(xs, offs, msks, w, None, cfg, LEVELS), 300, 'forward ' + name, fl)
 else:
     for blk in (0, 300):
         run(lambda: be.dcn_forward(xs, offs, msks, w, None, cfg, LEVELS), blk, 'forward')

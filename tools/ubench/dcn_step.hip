@@ -5,7 +5,7 @@
 //   * every result checked against a double-precision evaluation on the host for sampled elements (tools/ubench/dcn_ref.h,
 //     itself pinned against the oracle on CPU by tests/test_ubench_ref.py: tools may not link oracle/),
 //   * the backward run twice and compared bit for bit,
-//   * the same launches with debug bit 28 set (the kernels of dcn_kernels.h) as the A/B partner.
+//   * the same launches with LSN_DBG_GENERAL_GEMMS set (the kernels of dcn_kernels.h) as the A/B partner.
 //   hipcc --offload-arch=gfx950 -O2 tools/ubench/dcn_step.hip -o tools/ubench/dcn_step -ldl
 //   tools/ubench/dcn_step [tower|pyramid|both] [reps]
 #include <hip/hip_runtime.h>
@@ -234,9 +234,10 @@ int main(int argc, char **argv)
                 exit(3);
             }
         };
-        std::vector<float> keep[2];   // every gradient of mode 1 (new) and mode 0 (debug bit 28), concatenated
+        std::vector<float> keep[2];   // every gradient of mode 1 (new) and mode 0 (LSN_DBG_GENERAL_GEMMS), concatenated
         for (int mode = 1; mode >= 0; --mode) {
-            api.dbg(nullptr, mode ? (getenv("DCN_STEP_DBG") ? atoi(getenv("DCN_STEP_DBG")) : 0) : (1 << 28));   // DCN_STEP_DBG: debug bits of the default arm (A/B)
+            // DCN_STEP_DBG: the debug word of the default arm (A/B), a sum of LSN_DBG_* values
+            chk(api.dbg(nullptr, mode ? (getenv("DCN_STEP_DBG") ? (int)strtol(getenv("DCN_STEP_DBG"), nullptr, 0) : 0) : LSN_DBG_GENERAL_GEMMS), "debug word");
             const int64_t gbytes = api.ws_bytes(&s, n, lv.data());
             void *gws = nullptr;
             if (gbytes > 0) CK(hipMalloc(&gws, (size_t)gbytes));
@@ -264,7 +265,7 @@ int main(int argc, char **argv)
             for (const Level &L : la.lv) px += (double)B * L.Ho * L.Wo;
             const double gf = 2.0 * px * Co * C * K * 1e-9;
             printf("%-26s %s  gather workspace %.0f MB  forward %.1f us  backward %.1f us  (%.1f GFLOP per pass)\n", la.name.c_str(),
-                   mode ? "default kernels   " : "debug bit 28 (old)", gbytes / 1048576.0, tf * 1000 / reps, tb * 1000 / reps, gf);
+                   mode ? "default kernels      " : "LSN_DBG_GENERAL_GEMMS", gbytes / 1048576.0, tf * 1000 / reps, tb * 1000 / reps, gf);
             for (int i = 0; i < ne; ++i)
                 if (pe[i].launches > 0)
                     printf("    %-14s %3lld launches  %8.1f us each  %6.1f TF\n", pe[i].name, pe[i].launches,

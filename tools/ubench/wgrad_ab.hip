@@ -1,10 +1,10 @@
-// A/B of the dense-convolution weight gradient: the patch kernel of conv_wgrad_kernels.h (debug bit 28 set: the kernels of
-// dcn_mm_kernels.h are off) against dcn_wgrad_mm_kernel<NP, DENSE> forced with debug bit 27 (or, "rule": as the library routes), on the layer shapes of
-// the benchmark step (tools/bench_convs.py SH), through the C ABI only (no torch: the binary starts in a second).
+// A/B of the dense-convolution weight gradient: the patch kernel of conv_wgrad_kernels.h (LSN_DBG_GENERAL_GEMMS: the kernels
+// of dcn_mm_kernels.h are off) against the library's own routing (dcn_wgrad_mm_kernel<NP, DENSE> on the shapes it won on), on
+// the layer shapes of the benchmark step (tools/bench_convs.py SH), through the C ABI only (no torch: the binary starts in a second).
 // Each result is also checked against a double-precision sum on the host for 48 sampled weight elements.
 //   hipcc --offload-arch=gfx950 -O2 tools/ubench/wgrad_ab.hip -o tools/ubench/wgrad_ab -ldl
 //   tools/ubench/wgrad_ab [path to liblsnet_hip.so] [rule | bn]
-// "bn": the plain weight gradient (library routing) against lsn_conv2d_backward_weight_bn on the single-map shapes -- the
+// "rule" (the default): the comparison above.  "bn": the plain weight gradient (library routing) against lsn_conv2d_backward_weight_bn on the single-map shapes -- the
 // cost of the folded-norm reduce -- with grad_w = a G, grad_beta and grad_gamma checked against the plain call's results
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -50,7 +50,10 @@ struct Shape {
 
 int main(int argc, char **argv)
 {
-    const bool rule = argc > 2 && !strcmp(argv[2], "rule");   // "new" = the library's own routing instead of the forced kernel
+    if (argc > 2 && strcmp(argv[2], "rule") && strcmp(argv[2], "bn")) {
+        printf("usage: wgrad_ab [path to liblsnet_hip.so] [rule | bn]\n");
+        return 2;
+    }
     const char *so = argc > 1 ? argv[1] : "lsnet_amd/csrc/liblsnet_hip.so";
     void *h = dlopen(so, RTLD_NOW);
     if (!h) {
@@ -124,7 +127,10 @@ int main(int argc, char **argv)
             hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, 0, bnp + 2 * s.Co, (size_t)s.Co, 43u, 0.4f);   // var - 1
         }
         for (int mode = 0; mode < 2; ++mode) {   // 0: old kernels, 1: new
-            dbg(nullptr, bnmode ? 0 : mode == 0 ? (1 << 28) : rule ? 0 : (1 << 27));
+            if (dbg(nullptr, bnmode || mode == 1 ? 0 : LSN_DBG_GENERAL_GEMMS) != 0) {
+                printf("lsn_debug_phase_clocks: %s\n", lasterr());
+                return 2;
+            }
             CK(hipMalloc(&gw[mode], nW * 4));
             CK(hipMalloc(&gb[mode], (size_t)s.Co * 4));
             auto run = [&]() {
