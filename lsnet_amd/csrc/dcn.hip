@@ -188,6 +188,11 @@ static int i32(int64_t v, int *ok)
     return (int)v;
 }
 
+// 32-bit offsets: `elems` elements of `bytes_per` bytes stay below 2^31 (bytes_per = 1: a bound on the element count)
+static bool fits_i32(int64_t elems, int bytes_per = 1) { return elems * bytes_per < ((int64_t)1 << 31); }
+static int64_t in_elems(const DcnArgs &a, int i) { return (int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C; }
+static int64_t col_elems(const DcnArgs &a, int i) { return (int64_t)a.lv[i].P * a.kh * a.kw * a.C; }   // column-gradient rows
+
 template <typename KernelT>
 static int set_lds(KernelT kernel, size_t bytes)
 {
@@ -196,6 +201,38 @@ static int set_lds(KernelT kernel, size_t bytes)
         LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
+}
+
+// one launch of 256-thread workgroups with `lds` bytes of dynamic LDS
+template <typename KernelT, typename... Args>
+static int launch256(KernelT kern, dim3 grid, size_t lds, hipStream_t st, const Args &...args)
+{
+    if (int rc = set_lds(kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, args...);
+    LSN_HIP(hipGetLastError());
+    return 0;
+}
+
+// prow0 of every level, the launch-wide pixel-row numbering; returns the rows (the callers bound them)
+static int number_rows(DcnArgs &a)
+{
+    int rows = 0;
+    for (int i = 0; i < a.nlv; ++i) {
+        a.lv[i].prow0 = rows;
+        rows += a.lv[i].P;
+    }
+    return rows;
+}
+
+// tile0 of every level for tiles of `px` pixels; returns the tiles of the launch
+static int number_tiles(DcnArgs &a, int px)
+{
+    int tiles = 0;
+    for (int i = 0; i < a.nlv; ++i) {
+        a.lv[i].tile0 = tiles;
+        tiles += cdiv(a.lv[i].P, px);
+    }
+    return tiles;
 }
 
 // Fill the per-level part of DcnArgs from the public descriptors (NHWC pointers supplied here).
@@ -237,7 +274,7 @@ static int fill_levels(DcnArgs &a, const lsn_dcn_shape &s, int n, const lsn_dcn_
     a.gtap = nullptr;
     a.gtap_rows = 0;
     a.wg_vec = 0;
-    a.mm = 0;
+    a.mm = 0;   // (a field of the kernel argument that nothing reads any more: the route says which image wtp holds)
     a.opitch = s.out_pitch > 0 ? s.out_pitch : s.Co;
     a.wtp_bytes = 0;
     a.wg_part = a.wg_part_b = nullptr;
@@ -257,18 +294,13 @@ static bool vec_ok(const DcnArgs &a)
 }
 
 // ---- the kernels of dcn_mm_kernels.h (dense-convolution skeleton): conditions, weight image, launches ----
-static bool dcn_mm_env()
-{
-    return !dbg_on(LSN_DBG_GENERAL_GEMMS);   // the kernels of dcn_kernels.h only (tests, A/B runs)
-}
+static bool dcn_mm_env() { return !dbg_on(LSN_DBG_GENERAL_GEMMS); }   // (set: the kernels of dcn_kernels.h only -- tests, A/B runs)
 
 static bool mm_common_ok(const DcnArgs &a)
 {
     if (math_np() == 0 || a.groups != 1 || a.dg < 1 || a.C % a.dg != 0 || !dcn_mm_env()) return false;
-    for (int i = 0; i < a.nlv; ++i) {   // 32-bit buffer offsets
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C * 4 >= ((int64_t)1 << 31)) return false;
-        if ((int64_t)a.lv[i].P * a.opitch * 4 >= ((int64_t)1 << 31)) return false;
-    }
+    for (int i = 0; i < a.nlv; ++i)   // 32-bit buffer offsets
+        if (!fits_i32(in_elems(a, i), 4) || !fits_i32((int64_t)a.lv[i].P * a.opitch, 4)) return false;
     return true;
 }
 
@@ -278,7 +310,7 @@ static bool mm_fwd_ok(const DcnArgs &a)
 {
     if (!mm_common_ok(a) || (a.C / a.dg) % 32 != 0 || a.Co % 128 != 0) return false;
     if (dcn_fwd_mm_lds_bytes(mm_npl(), a.kh * a.kw * a.dg) > 80 * 1024) return false;
-    return cv_wfrag_bytes(a.Co, a.kh * a.kw, a.C, mm_npl()) < ((size_t)1 << 31);
+    return fits_i32((int64_t)cv_wfrag_bytes(a.Co, a.kh * a.kw, a.C, mm_npl()));
 }
 
 // backward-data GEMM as a 1x1 convolution (conv.hip conv_mm_rows) + corner sums in the gather pass: every level that
@@ -292,39 +324,14 @@ static bool mm_bwd_ok(const DcnArgs &a)
     for (int i = 0; i < a.nlv; ++i)
         if ((a.lv[i].goff || a.lv[i].gmsk) && !a.lv[i].gx) return false;
     const size_t wb = cv_wfrag_bytes(a.kh * a.kw * a.C, 1, a.Co, mm_npl());
-    return wb < ((size_t)1 << 31) && wb <= (size_t)8 * a.Co * a.kh * a.kw * a.C;
-}
-
-// weight image in fragment order into `dst` (forward: (Co, K, C) as it lies; backward: the transposed 1x1 view with
-// N = K * C columns and the reduction over Co)
-// (prepared: the caller's image is already there -- lsn_dcn_shape.weights_prepared)
-static int mm_prepare_weights(DcnArgs &a, bool backward, void *dst, hipStream_t st, bool prepared = false)
-{
-    const int K = a.kh * a.kw;
-    const int Co = backward ? K * a.C : a.Co, Kd = backward ? 1 : K, C = backward ? a.Co : a.C;
-    TapSub ts = {0, 1, 1, 0, 1, 1, 1};
-    unsigned short *out = reinterpret_cast<unsigned short *>(dst);
-    if (!prepared) {
-        WfragJob j = {};
-        j.w = a.w, j.out = out, j.Co = Co, j.K = Kd, j.C = C, j.flipT = backward ? 1 : 0, j.ts = ts;
-        const long long total = wfrag_threads(j);
-        const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (int rc = split_dispatch(math_np(), [&](auto np) {
-                hipLaunchKernelGGL(conv_wfrag_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(blocks), dim3(256), 0, st, j);
-                return 0;
-            }))
-            return rc;
-        LSN_HIP(hipGetLastError());
-    }
-    a.wtp = out;
-    a.wtp_bytes = (int)cv_wfrag_bytes(Co, Kd, C, mm_npl());
-    a.mm = 1;
-    return 0;
+    return fits_i32((int64_t)wb) && wb <= (size_t)8 * a.Co * a.kh * a.kw * a.C;
 }
 
 // Work distribution of a forward launch (dcn_mm_kernels.h DcnSk).  The chip holds 512 workgroups of the kernel; whole rounds
-// stay one workgroup per tile, the r tiles of the last round are cut into pieces of >= 4 chunks spread evenly over up to 512
-// workgroups.  Measured (tools/ubench/dcn_step, LSN_DBG_FWD_SK_NEVER = whole tiles only, profiles/r6_dcn_sk.txt): the pyramid launch
+// stay one workgroup per tile, the chunks of the r tiles of the last round are spread evenly over min(chunks / 4, cap) pieces
+// per tile (cap: 4 in a launch of at most one round, 16 in a longer one) and at most 512 pieces in all, one workgroup each: a
+// piece has about 4 chunks or more, with no guaranteed minimum (chunks / 4 rounds down).  Measured
+// (tools/ubench/dcn_step, LSN_DBG_FWD_SK_NEVER = whole tiles only, profiles/r6_dcn_sk.txt): the pyramid launch
 // (2 100 tiles: four rounds and 52 tiles) 780 -> 759 us; the tower launch (700 tiles: one round and 188 tiles) 278 -> 283 us --
 // its second round runs one workgroup per CU, which has the matrix pipe to itself and finishes in ~0.65 of a round, so the
 // even split has little to return and the pieces' table rebuild and hand-over cost more.  Hence: launches of two rounds and
@@ -360,18 +367,9 @@ static int launch_fwd_mm_cfg(const DcnArgs &a, hipStream_t st)
     const int blocks = a.ntiles * (a.Co / BN);
     DcnSk sk;
     dcn_sk_plan(blocks, a.kh * a.kw * (a.C / 32), &sk);
-    if (sk.sk_n) {
-        if (int rc = conv_sk_scratch((size_t)2 * sk.sk_n * 64 * BN, &sk.part, &sk.cnt, st)) return rc;
-        auto k = dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, true>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(sk.n_dp + sk.sk_n), dim3(256), lds, st, a, a.wtp, a.wtp_bytes, sk);
-    } else {
-        auto k = dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, false>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, a, a.wtp, a.wtp_bytes, sk);
-    }
-    LSN_HIP(hipGetLastError());
-    return 0;
+    if (!sk.sk_n) return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, false>, dim3(blocks), lds, st, a, a.wtp, a.wtp_bytes, sk);
+    if (int rc = conv_sk_scratch((size_t)2 * sk.sk_n * 64 * BN, &sk.part, &sk.cnt, st)) return rc;
+    return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, true>, dim3(sk.n_dp + sk.sk_n), lds, st, a, a.wtp, a.wtp_bytes, sk);
 }
 
 static int launch_forward_mm(const DcnArgs &a, hipStream_t st)
@@ -392,89 +390,66 @@ static int launch_forward_t(const DcnArgs &a, hipStream_t st)
     const int Cog = a.Co / a.groups, KD = a.kh * a.kw * a.dg;
     const size_t lds = (size_t)(BM + BN) * 33 * 4 + (size_t)BM * KD * sizeof(Tap);
     dim3 grid(a.ntiles, cdiv(Cog, BN), a.groups);
-    if (vec_ok(a)) {
-        auto k = dcn_fwd_kernel<BM, BN, WM, WN, true>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);
-    } else {
-        auto k = dcn_fwd_kernel<BM, BN, WM, WN, false>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);
-    }
-    LSN_HIP(hipGetLastError());
-    return 0;
+    return vec_ok(a) ? launch256(dcn_fwd_kernel<BM, BN, WM, WN, true>, grid, lds, st, a)
+                     : launch256(dcn_fwd_kernel<BM, BN, WM, WN, false>, grid, lds, st, a);
 }
 
 // the split one-workgroup-per-CU kernel (dcn_fwd_xn_kernel) needs float4 rows and 32-bit byte offsets into x and w
 static bool xn_ok(const DcnArgs &a)
 {
     if (a.Co / a.groups <= 64 || !vec_ok(a)) return false;
-    if ((int64_t)a.Co * a.kh * a.kw * (a.C / a.groups) * 4 >= (int64_t)1 << 31) return false;
+    if (!fits_i32((int64_t)a.Co * a.kh * a.kw * (a.C / a.groups), 4)) return false;
     for (int i = 0; i < a.nlv; ++i)
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C * 4 >= (int64_t)1 << 31) return false;
+        if (!fits_i32(in_elems(a, i), 4)) return false;
     return true;
 }
 
 // ---- grouped calls (dcn_grouped_kernels.h): ResNeXt's 64 groups of 8 / 16 / 32 channels ----
+static bool grouped_inputs_ok(const DcnArgs &a)   // 16-byte loads at 32-bit element offsets
+{
+    for (int i = 0; i < a.nlv; ++i)
+        if (!fits_i32(in_elems(a, i)) || (reinterpret_cast<uintptr_t>(a.lv[i].x) & 15) != 0) return false;
+    return true;
+}
+
 static bool grouped_fwd_ok(const DcnArgs &a)
 {
     if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C) return false;
     const int cg = a.C / a.groups;
     if (!(cg == 8 || cg == 16 || cg == 32) || a.C % GF_CH != 0 || a.C % a.dg != 0 || (a.C / a.dg) % GF_CH != 0) return false;
-    if (dcn_fwd_grouped_lds_bytes(a.kh * a.kw) > 64 * 1024) return false;
-    for (int i = 0; i < a.nlv; ++i)
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(a.lv[i].x) & 15) != 0)
-            return false;
-    return true;
+    return dcn_fwd_grouped_lds_bytes(a.kh * a.kw) <= 64 * 1024 && grouped_inputs_ok(a);
 }
 
 static int launch_forward_grouped(const DcnArgs &a_in, hipStream_t st)
 {
     DcnArgs a = a_in;
-    int tiles = 0;
-    for (int i = 0; i < a.nlv; ++i) {
-        a.lv[i].tile0 = tiles;
-        tiles += cdiv(a.lv[i].P, GF_PX);
-    }
-    a.ntiles = tiles;
+    a.ntiles = number_tiles(a, GF_PX);
     ProfScope prof(PROF_FWD, a, st);
     const size_t lds = dcn_fwd_grouped_lds_bytes(a.kh * a.kw);
-    const dim3 grid(tiles * (a.C / GF_CH));
-    auto go = [&](auto kern) -> int {
-        if (int rc = set_lds(kern, lds)) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-        LSN_HIP(hipGetLastError());
-        return 0;
-    };
+    const dim3 grid(a.ntiles * (a.C / GF_CH));
     switch (a.C / a.groups) {
-    case 8: return go(dcn_fwd_grouped_kernel<8>);
-    case 16: return go(dcn_fwd_grouped_kernel<16>);
-    default: return go(dcn_fwd_grouped_kernel<32>);
+    case 8: return launch256(dcn_fwd_grouped_kernel<8>, grid, lds, st, a);
+    case 16: return launch256(dcn_fwd_grouped_kernel<16>, grid, lds, st, a);
+    default: return launch256(dcn_fwd_grouped_kernel<32>, grid, lds, st, a);
     }
 }
 
-static int launch_forward(const DcnArgs &a, hipStream_t st)
+// exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU
+static int launch_forward_fp32(const DcnArgs &a, hipStream_t st)
 {
-    if (a.mm) return launch_forward_mm(a, st);
-    if (grouped_fwd_ok(a)) return launch_forward_grouped(a, st);
-    const int np = math_np(), KDf = a.kh * a.kw * a.dg;
-    // exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU
-    if (np == 0 || !xn_ok(a) || xn_lds_bytes(split_npl(np), KDf) > 160 * 1024) {
-        ProfScope prof(PROF_FWD, a, st);
-        return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, st) : launch_forward_t<64, 256, 1, 4>(a, st);
-    }
+    ProfScope prof(PROF_FWD, a, st);
+    return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, st) : launch_forward_t<64, 256, 1, 4>(a, st);
+}
+
+// planes: a.wtp holds the weights as dcn_prepare_w_kernel split them; otherwise every block splits its own
+static int launch_forward_xn(const DcnArgs &a, bool planes, hipStream_t st)
+{
     dim3 grid(a.ntiles, cdiv(a.Co / a.groups, PIPE_BN), a.groups);
     ProfScope prof(PROF_FWD, a, st);
-    auto gox = [&](auto kern, size_t ldsn) -> int {
-        if (int rc = set_lds(kern, ldsn)) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), ldsn, st, a);
-        LSN_HIP(hipGetLastError());
-        return 0;
-    };
-    return split_dispatch(np, [&](auto npc) {
+    return split_dispatch(math_np(), [&](auto npc) {
         constexpr int NP = decltype(npc)::value;
-        const size_t ldsn = xn_lds_bytes<NP>(KDf);
-        return a.wtp ? gox(dcn_fwd_xn_kernel<true, NP>, ldsn) : gox(dcn_fwd_xn_kernel<false, NP>, ldsn);
+        const size_t ldsn = xn_lds_bytes<NP>(a.kh * a.kw * a.dg);
+        return planes ? launch256(dcn_fwd_xn_kernel<true, NP>, grid, ldsn, st, a) : launch256(dcn_fwd_xn_kernel<false, NP>, grid, ldsn, st, a);
     });
 }
 
@@ -483,36 +458,30 @@ static int launch_bwd_data_t(const DcnArgs &a, hipStream_t st)
 {
     const int KD = a.kh * a.kw * a.dg;
     const size_t lds = (size_t)RED * 32 * 4 + (size_t)BWD_BM * KD * (sizeof(Tap) + 12);
-    if (vec_ok(a)) {
-        auto k = dcn_bwd_data_kernel<RED, true>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(256), lds, st, a);
-    } else {
-        auto k = dcn_bwd_data_kernel<RED, false>;
-        if (int rc = set_lds(k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(256), lds, st, a);
-    }
-    LSN_HIP(hipGetLastError());
-    return 0;
+    return vec_ok(a) ? launch256(dcn_bwd_data_kernel<RED, true>, dim3(a.ntiles), lds, st, a)
+                     : launch256(dcn_bwd_data_kernel<RED, false>, dim3(a.ntiles), lds, st, a);
 }
 
-static bool bwd_x3_ok(const DcnArgs &a)
+// 32-bit buffer offsets into the input and into every level's column-gradient rows (backward-data, every kernel in front
+// of the gather pass)
+static bool bwd_offsets_ok(const DcnArgs &a)
 {
-    if (math_np() == 0 || a.wtp == nullptr || a.groups != 1) return false;
-    if (a.Co > 256 || a.Co % 8 != 0 || a.C % 4 != 0) return false;
-    if ((int64_t)a.kh * a.kw * a.C * a.Co * 6 >= ((int64_t)1 << 31)) return false;
-    if (bwd_xn_lds_bytes(math_np(), a.kh * a.kw * a.dg) > 80 * 1024) return false;
-    for (int i = 0; i < a.nlv; ++i) {   // 32-bit buffer offsets into the input and the level's column-gradient rows
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C * 4 >= ((int64_t)1 << 31)) return false;
-        if ((int64_t)a.lv[i].P * a.kh * a.kw * a.C * 4 >= ((int64_t)1 << 31)) return false;
-    }
+    for (int i = 0; i < a.nlv; ++i)
+        if (!fits_i32(in_elems(a, i), 4) || !fits_i32(col_elems(a, i), 4)) return false;
     return true;
 }
 
-static bool bwd_colbuf_env()
+// round 2's split GEMM (dcn_bwd_data_xn_kernel) on the transposed weight planes the caller's `workspace` holds
+static bool bwd_x3_ok(const DcnArgs &a)
 {
-    return !dbg_on(LSN_DBG_ATOMIC_SCATTER);   // the atomic scatter kernels (tests)
+    if (math_np() == 0 || a.groups != 1) return false;
+    if (a.Co > 256 || a.Co % 8 != 0 || a.C % 4 != 0) return false;
+    if (!fits_i32((int64_t)a.kh * a.kw * a.C * a.Co, 6)) return false;
+    if (bwd_xn_lds_bytes(math_np(), a.kh * a.kw * a.dg) > 80 * 1024) return false;
+    return bwd_offsets_ok(a);
 }
+
+static bool bwd_colbuf_env() { return !dbg_on(LSN_DBG_ATOMIC_SCATTER); }   // (set: the atomic scatter kernels -- tests)
 
 // Exact-fp32 column gradients (dcn_gcol_grouped_kernel: fmaf chains per group) in front of the gather pass: grouped calls
 // (config 4: 64 groups) in every math mode, and -- round 6 -- EVERY call of LSN_MATH_FP32: the exact mode used to scatter
@@ -524,24 +493,9 @@ static bool bwd_grouped_ok(const DcnArgs &a)
     if (a.groups <= 1 && math_np() != 0) return false;
     if (a.C % a.groups != 0 || a.Co % a.groups != 0 || (a.C / a.groups) % 4 != 0 || a.C % a.dg != 0) return false;
     if ((a.C / a.dg) % 4 != 0 || !bwd_colbuf_env()) return false;
-    for (int i = 0; i < a.nlv; ++i) {
+    for (int i = 0; i < a.nlv; ++i)
         if ((a.lv[i].goff || a.lv[i].gmsk) && !a.lv[i].gx) return false;
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C * 4 >= ((int64_t)1 << 31)) return false;
-        if ((int64_t)a.lv[i].P * a.kh * a.kw * a.C * 4 >= ((int64_t)1 << 31)) return false;
-    }
-    return true;
-}
-
-// the atomic-free path (column gradients + gather): served by the dense GEMM (mm_bwd_ok: any Co) or by round 2's GEMM
-static bool bwd_gather_ok(const DcnArgs &a)
-{
-    if (bwd_grouped_ok(a)) return true;
-    if (a.wtp == nullptr) return false;
-    if (bwd_x3_ok(a)) return true;
-    if (!mm_bwd_ok(a)) return false;
-    for (int i = 0; i < a.nlv; ++i)   // 32-bit offsets into the level's column-gradient rows
-        if ((int64_t)a.lv[i].P * a.kh * a.kw * a.C * 4 >= ((int64_t)1 << 31)) return false;
-    return true;
+    return bwd_offsets_ok(a);
 }
 
 // ---- atomic-free grad_input: workspace plan of the bin / scan / fill / sort / gather sequence (dcn_gather_kernels.h) ----
@@ -561,7 +515,8 @@ struct GatherPlan {
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Fills prow0 / abase of the levels and the plan.  gx pointers: levels with the same grad_input share an anchor grid.
-static void gather_plan(DcnArgs &a, GatherPlan &pl)
+// all_anchor: every group on the per-anchor path (route_backward says when).
+static void gather_plan(DcnArgs &a, GatherPlan &pl, bool all_anchor)
 {
     pl.ok = false;
     const int K = a.kh * a.kw, KD = K * a.dg;
@@ -605,9 +560,8 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl)
     aa.ng = 0, aa.NA = 0;
     pl.anchor_pixels = 0, pl.block_samples = 0;
     {
-        // anchor path: every group when the unweighted-GEMM pipeline serves the call (its corner sums are cheapest per
+        // anchor path: every group when the unweighted-GEMM pipeline can serve the call (its corner sums are cheapest per
         // anchor), otherwise the groups above the threshold.  Long-list groups first: they get four waves per anchor.
-        const bool all_anchor = mm_bwd_ok(a) || bwd_grouped_ok(a);
         GatherGrp keep[MAXLV];
         bool to_anchor[MAXLV], is_long[MAXLV];
         int nk = 0;
@@ -676,6 +630,157 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl)
     pl.ok = true;
 }
 
+// Pixel splits of a weight-gradient launch: the grid (columns x splits x co blocks) fills ONE round of the blocks the chip
+// holds at once (256 CUs x per_cu), rounded DOWN.  Measured on the benchmark step (profiles/r2_wgrad_rounds.txt): the
+// old cdiv(1024, 36) = 29 splits made 1044 blocks = two full rounds plus a third with 20 blocks (0.88 ms per DCN
+// launch); 28 splits 0.68 ms; one round instead of two is the same for the DCN launches and 1.1 ms / step faster over
+// the dense layers (half the fp32 atomics of the epilogues).
+static int wgrad_splits(int cols, int per_cu)
+{
+    const int slots = 256 * per_cu;
+    int s = slots / cols;
+    return s < 1 ? 1 : s;
+}
+
+// weight gradient on the kernels of dcn_mm_kernels.h (it also needs the tap table of the gather pass: route_backward)
+static bool mm_wgrad_ok(const DcnArgs &a) { return mm_common_ok(a) && a.Co % 256 == 0 && (a.C / a.dg) % 64 == 0; }
+// ... and its fragment-order image of grad_output (nchunks 32-pixel chunks) at 32-bit byte offsets
+static bool wgrad_mm_image_ok(const DcnArgs &a, int nchunks) { return fits_i32((int64_t)nchunks * 2 * (a.Co / 32) * mm_npl(), 1024); }
+
+static bool grouped_wgrad_ok(const DcnArgs &a)
+{
+    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C || a.kh * a.kw > 9) return false;
+    const int cg = a.C / a.groups;
+    if (!(cg == 4 || cg == 8 || cg == 16 || cg == 32) || ((int64_t)a.C * cg) % 256 != 0 || a.C % a.dg != 0) return false;
+    const int nch = cg >= 16 ? cg : 256 / cg;
+    if ((a.C / a.dg) % nch != 0 || a.C % nch != 0) return false;
+    return grouped_inputs_ok(a);
+}
+
+// ---- the route of a call: which kernel serves each pass and what else that fixes.  route_forward / route_backward decide
+// it once, before anything is launched; they are the only callers of the *_ok predicates and of gather_plan, and the three
+// queries of the C ABI (lsn_dcn_backward_workspace_bytes, lsn_dcn_prepared_ok, lsn_dcn_pitched_ok) read their answers. ----
+enum FwdKernel { FWD_MM, FWD_GROUPED, FWD_XN_PLANES, FWD_XN, FWD_FP32 };
+// GATHER_*: column gradients from that kernel, then the atomic-free gather pass; SCATTER_*: fp32 atomics into grad_input
+enum DataKernel { DATA_NONE, GATHER_GROUPED, GATHER_MM, GATHER_XN, SCATTER_XN, SCATTER_FP32 };
+enum WgradKernel { WG_NONE, WG_GROUPED, WG_MM, WG_XN_ORDERED, WG_XN_ATOMIC, WG_FP32_ORDERED, WG_FP32_ATOMIC };
+// what the caller's `workspace` gets: nothing, the fragment-order image of dcn_mm_kernels.h (the only one a caller may
+// hand over prepared), the split bf16 planes (forward) or the split and transposed ones (backward)
+enum WeightImage { IMG_NONE, IMG_FRAGMENT, IMG_PLANES, IMG_PLANES_T };
+
+struct DcnRoute {
+    FwdKernel fwd = FWD_FP32;
+    DataKernel data = DATA_NONE;
+    WgradKernel wgrad = WG_NONE;
+    WeightImage image = IMG_NONE;
+    bool pitched = false;    // out_pitch != Co is served (lsn_dcn_pitched_ok)
+    bool prepared = false;   // weights_prepared is served (lsn_dcn_prepared_ok)
+    int gcol_ks = 0;         // GATHER_GROUPED: k-steps of dcn_gcol_mfma_kernel; 0: the fmaf chains of dcn_gcol_grouped_kernel
+    int wg_steps = 0;        // weight gradient: 32-pixel steps of all levels
+    bool own_gather_ws = false;        // LSN_NCHW without the caller's gather workspace: plan.bytes of the call's own scratch
+    GatherPlan plan;                   // GATHER_*: computed here, once
+    bool gather() const { return data == GATHER_GROUPED || data == GATHER_MM || data == GATHER_XN; }
+};
+
+// Order: mm -> grouped -> xn -> fp32.  The reference-layout (LSN_NCHW) entry points take the same kernels but neither
+// out_pitch nor a prepared image.
+static DcnRoute route_forward(const DcnArgs &a, const lsn_dcn_shape &s, lsn_layout layout)
+{
+    DcnRoute r;
+    const int np = math_np();
+    if (s.workspace && mm_fwd_ok(a)) {
+        r.fwd = FWD_MM, r.image = IMG_FRAGMENT;
+    } else if (grouped_fwd_ok(a)) {
+        r.fwd = FWD_GROUPED;
+    } else if (np != 0 && xn_ok(a) && xn_lds_bytes(split_npl(np), a.kh * a.kw * a.dg) <= 160 * 1024) {
+        r.fwd = FWD_XN;   // with a workspace the weights are split once instead of in every block
+        if (s.workspace && (a.C / a.groups) % 8 == 0) r.fwd = FWD_XN_PLANES, r.image = IMG_PLANES;
+    }
+    r.pitched = r.prepared = layout == LSN_NHWC && r.fwd == FWD_MM;
+    return r;
+}
+
+// k-steps of the fp32-MFMA column gradients (dcn_grouped_kernels.h dcn_gcol_mfma_kernel); 0: the fmaf-chain kernel
+static int gcol_mfma_ksteps(const DcnArgs &a)
+{
+    const int Cg = a.C / a.groups, Cog = a.Co / a.groups;
+    if (a.C % GC_COLS != 0 || a.opitch % 4 != 0) return 0;
+    for (int i = 0; i < a.nlv; ++i)
+        if ((reinterpret_cast<uintptr_t>(a.lv[i].gout) & 15) != 0) return 0;
+    if (a.groups == 1) return (a.Co == 64 || a.Co == 128 || a.Co == 256) ? a.Co / 4 : 0;
+    return (Cog == Cg && (Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32)) ? (Cg == 32 ? 8 : 4) : 0;
+}
+
+// grid of the split weight-gradient kernels (dcn_wgrad_kernel / dcn_wgrad_xn_kernel): columns, co blocks; returns the pixel splits
+static int wgrad_split_grid(const DcnArgs &a, int nsteps, int *ncol, int *nz)
+{
+    const int K = a.kh * a.kw, Cg = a.C / a.groups, Cog = a.Co / a.groups;
+    *ncol = a.groups * K * (Cg / a.SL) * cdiv(a.SL, WG_BN), *nz = cdiv(Cog, WG_BM);
+    int s = wgrad_splits(*ncol * *nz, 2);   // 2 resident blocks per CU (246 VGPRs, 78 KB LDS)
+    if (s > nsteps) s = nsteps;
+    if (s < 1) s = 1;
+    return s > 65535 ? 65535 : s;
+}
+
+// gws / gws_bytes: the caller's gather workspace.  want_wgrad: grad_weight is asked for (the queries answer for that case).
+// Backward-data: the gather path where a column-gradient kernel serves the call -- grouped (groups > 1, or any call of
+// LSN_MATH_FP32), else mm, else xn -- and a gather workspace holds the plan; else scatter xn; else the fp32 scatter.
+// Weight gradient: grouped (dense grad_output, 4 | weight elements) -> mm (reads the gather pass's tap table) -> the split
+// kernels.  A prepared image is served by GATHER_MM (so: groups = 1, a split-bf16 mode, even Co, some data gradient), out_pitch
+// by GATHER_MM and -- when grad_weight is asked for -- WG_MM; neither by the reference-layout (LSN_NCHW) entry points, which
+// get the call's own gather scratch instead of the caller's.
+static DcnRoute route_backward(DcnArgs &a, const lsn_dcn_shape &s, lsn_layout layout, const void *gws, size_t gws_bytes,
+                               bool want_wgrad)
+{
+    DcnRoute r;
+    const int np = math_np(), K = a.kh * a.kw;
+    bool any_data = false;
+    for (int i = 0; i < a.nlv; ++i) any_data = any_data || a.lv[i].gx || a.lv[i].goff || a.lv[i].gmsk;
+    if (any_data) {
+        // can_split: `workspace` gets a bf16 image of the weights (8 bytes per weight element: even Co for the planes)
+        const bool can_split = s.workspace && np && a.groups == 1 && a.Co % 2 == 0;
+        const bool grouped = bwd_grouped_ok(a), mm = mm_bwd_ok(a), x3 = can_split && bwd_x3_ok(a);
+        const DataKernel cand = !bwd_colbuf_env()                         ? DATA_NONE
+                                : grouped                                 ? GATHER_GROUPED
+                                : (can_split && mm && bwd_offsets_ok(a)) ? GATHER_MM
+                                : x3                                      ? GATHER_XN
+                                                                          : DATA_NONE;
+        bool fits = false;
+        if (cand != DATA_NONE && (gws || layout == LSN_NCHW)) {
+            // (all_anchor keys on what the arguments admit, not on the kernel taken: the workspace size a caller asked for
+            // without `workspace` serves the call with it)
+            gather_plan(a, r.plan, mm || grouped);
+            r.own_gather_ws = !gws && r.plan.ok;
+            fits = r.plan.ok && (r.own_gather_ws || r.plan.bytes <= gws_bytes);
+        }
+        r.data = fits ? cand : x3 ? SCATTER_XN : SCATTER_FP32;
+        if (r.data == GATHER_GROUPED) r.gcol_ks = gcol_mfma_ksteps(a);
+        // (the transposed planes are written for every call that can split, also where the fp32 scatter then ignores them)
+        r.image = r.data == GATHER_MM ? IMG_FRAGMENT : can_split ? IMG_PLANES_T : IMG_NONE;
+        r.prepared = layout == LSN_NHWC && r.data == GATHER_MM;
+    }
+    if (want_wgrad) {
+        int64_t rows = 0, steps = 0;
+        for (int i = 0; i < a.nlv; ++i) rows += a.lv[i].P, steps += cdiv(a.lv[i].P, WG_BP);
+        r.wg_steps = (int)steps;
+        const size_t nW = (size_t)a.Co * K * (a.C / a.groups);
+        // the tap table of the gather pass, 16-byte aligned (the call's own scratch is)
+        const bool tap_table = r.gather() && (r.own_gather_ws || ((reinterpret_cast<uintptr_t>(gws) + r.plan.o_gtap) & 15) == 0);
+        if (grouped_wgrad_ok(a) && a.opitch == a.Co && nW % 4 == 0 && rows < ((int64_t)1 << 30)) {
+            r.wgrad = WG_GROUPED;
+        } else if (mm_wgrad_ok(a) && tap_table && wgrad_mm_image_ok(a, r.wg_steps)) {
+            r.wgrad = WG_MM;
+        } else {
+            // one partial gradient per pixel split + an ordered reduce instead of fp32 atomics (deterministic) where they fit
+            int ncol, nz;
+            const int splits = wgrad_split_grid(a, r.wg_steps, &ncol, &nz);
+            const bool ordered = nW % 4 == 0 && (size_t)splits * (nW + a.Co) * sizeof(float) <= ((size_t)256 << 20);
+            r.wgrad = np ? (ordered ? WG_XN_ORDERED : WG_XN_ATOMIC) : (ordered ? WG_FP32_ORDERED : WG_FP32_ATOMIC);
+        }
+    }
+    r.pitched = layout == LSN_NHWC && r.data == GATHER_MM && (!want_wgrad || r.wgrad == WG_MM);
+    return r;
+}
 
 // Tap groups of the split backward-data GEMM (grid.y): the launch runs in ceil(tiles x groups / 512) rounds of the 512
 // resident blocks (2 per CU) with blocks 1 / groups as long, plus a per-block prologue (gout tile -> registers, sampling
@@ -737,9 +842,9 @@ static int side_stream(hipStream_t st, SideStream **out)
 // and ran the per-anchor sums of band i on the side stream beside the GEMM of band i + 1, the column gradients of a band
 // still in the Infinity Cache: tower +7 % slower, pyramid unchanged, profiles/r5_band_pipeline.txt.  GEMM and sums are both
 // bound by the memory system; removed.)
-template <int NP>
-static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipStream_t st_main)
+static int launch_bwd_gather(DcnArgs &a, DcnRoute &r, unsigned char *ws, hipStream_t st_main)
 {
+    GatherPlan &pl = r.plan;
     a.gcol = reinterpret_cast<float *>(ws + pl.o_gcol);
     int *cnt = reinterpret_cast<int *>(ws + pl.o_cnt), *start = reinterpret_cast<int *>(ws + pl.o_start);
     int *sanchor = reinterpret_cast<int *>(ws + pl.o_anchor), *srank = reinterpret_cast<int *>(ws + pl.o_rank);
@@ -749,7 +854,7 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
     a.gtap_rows = pl.nsamples / (a.kh * a.kw * a.dg);
     // lists on the side stream only beside the dense GEMM (the other column-gradient kernels read the tap table)
     SideStream *side = nullptr;
-    if (a.mm && a.groups == 1)
+    if (r.data == GATHER_MM)
         if (int rc = side_stream(st_main, &side)) return rc;
     hipStream_t st = side ? side->side : st_main;
     if (side) {
@@ -772,39 +877,23 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
         LSN_HIP(hipEventRecord(side->join, side->side));
         st = st_main;
     }
+    bool any_off = false;
+    for (int i = 0; i < a.nlv; ++i) any_off = any_off || a.lv[i].goff || a.lv[i].gmsk;
     float *Hb = nullptr;
-    const bool grouped = a.groups > 1 || NP == 0;   // (NP = 0: LSN_MATH_FP32, every call)
-    if (grouped) {   // exact-fp32 column gradients per group, unweighted; the gather pass does the rest as for the dense GEMM
-        int ks = 0;   // k-steps of the fp32-MFMA form (dcn_grouped_kernels.h dcn_gcol_mfma_kernel); 0: the fmaf-chain kernel
-        const int Cg = a.C / a.groups, Cog = a.Co / a.groups;
-        if (a.C % GC_COLS == 0 && a.opitch % 4 == 0) {
-            if (a.groups == 1 && (a.Co == 64 || a.Co == 128 || a.Co == 256)) ks = a.Co / 4;
-            if (a.groups > 1 && Cog == Cg && (Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32)) ks = Cg == 32 ? 8 : 4;
-            for (int i = 0; i < a.nlv; ++i)
-                if ((reinterpret_cast<uintptr_t>(a.lv[i].gout) & 15) != 0) ks = 0;
-        }
-        if (ks) {
+    switch (r.data) {
+    case GATHER_GROUPED:   // exact-fp32 column gradients per group, unweighted; the gather pass does the rest as for the dense GEMM
+        if (r.gcol_ks) {
             DcnArgs g = a;
-            int tiles = 0;
-            for (int i = 0; i < g.nlv; ++i) {
-                g.lv[i].tile0 = tiles;
-                tiles += cdiv(g.lv[i].P, GC_PX);
-            }
             const int nred = a.groups == 1 ? a.Co : GC_COLS;
             const size_t lds = dcn_gcol_mfma_lds_bytes(nred);
-            const dim3 grid(tiles * (a.C / GC_COLS));
-            auto go = [&](auto kern) -> int {
-                if (int rc = set_lds(kern, lds)) return rc;
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, g, nred);
-                return 0;
-            };
+            const dim3 grid(number_tiles(g, GC_PX) * (a.C / GC_COLS));
             int rc = 0;
-            switch (ks) {
-            case 4: rc = go(dcn_gcol_mfma_kernel<4>); break;
-            case 8: rc = go(dcn_gcol_mfma_kernel<8>); break;
-            case 16: rc = go(dcn_gcol_mfma_kernel<16>); break;
-            case 32: rc = go(dcn_gcol_mfma_kernel<32>); break;
-            default: rc = go(dcn_gcol_mfma_kernel<64>); break;
+            switch (r.gcol_ks) {
+            case 4: rc = launch256(dcn_gcol_mfma_kernel<4>, grid, lds, st, g, nred); break;
+            case 8: rc = launch256(dcn_gcol_mfma_kernel<8>, grid, lds, st, g, nred); break;
+            case 16: rc = launch256(dcn_gcol_mfma_kernel<16>, grid, lds, st, g, nred); break;
+            case 32: rc = launch256(dcn_gcol_mfma_kernel<32>, grid, lds, st, g, nred); break;
+            default: rc = launch256(dcn_gcol_mfma_kernel<64>, grid, lds, st, g, nred); break;
             }
             if (rc) return rc;
         } else {
@@ -812,30 +901,31 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
             const int blocks = (int)((nquads + 255) / 256 < 16384 ? (nquads + 255) / 256 : 16384);
             hipLaunchKernelGGL(dcn_gcol_grouped_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, nquads);
         }
-        for (int i = 0; i < a.nlv; ++i)
-            if (a.lv[i].goff || a.lv[i].gmsk) Hb = reinterpret_cast<float *>(ws + pl.o_H);
-    } else if (a.mm) {   // the dense kernel writes the unweighted column gradients; everything else happens in the gather pass
+        if (any_off) Hb = reinterpret_cast<float *>(ws + pl.o_H);
+        break;
+    case GATHER_MM: {   // the dense kernel writes the unweighted column gradients; everything else happens in the gather pass
         const float *xs[MAXLV];
         float *outs[MAXLV];
         int rows[MAXLV];
-        bool any_off = false;
         for (int i = 0; i < a.nlv; ++i) {
             xs[i] = a.lv[i].gout;
             outs[i] = a.gcol + (size_t)a.lv[i].prow0 * a.kh * a.kw * a.C;
             rows[i] = a.lv[i].P;
-            any_off = any_off || a.lv[i].goff || a.lv[i].gmsk;
         }
         if (int rc = conv_mm_rows(a.nlv, xs, outs, rows, a.Co, a.opitch, a.kh * a.kw * a.C, a.wtp, st)) return rc;
-        if (side) LSN_HIP(hipStreamWaitEvent(st_main, side->join, 0));
+        LSN_HIP(hipStreamWaitEvent(st_main, side->join, 0));
         if (any_off) Hb = reinterpret_cast<float *>(ws + pl.o_H);
-    } else if constexpr (NP != 0) {
-        size_t lds = bwd_xn_lds_bytes(NP, a.kh * a.kw * a.dg);
-        if (int rc = set_lds(dcn_bwd_data_xn_kernel<NP, true>, lds)) return rc;
-        hipLaunchKernelGGL((dcn_bwd_data_xn_kernel<NP, true>), dim3(a.ntiles, bwd_tap_groups(a)), dim3(256), lds, st, a);
-    } else {
-        return fail(LSN_ERR_RUNTIME, "deformable backward: exact mode without the exact column-gradient kernel");
+        break;
     }
-    pl.ga.raw = pl.aa.raw = (a.mm || grouped) ? 1 : 0;
+    default:   // GATHER_XN: mask-weighted column gradients, offset / mask gradients in the same kernel
+        if (int rc = split_dispatch(math_np(), [&](auto npc) {
+                constexpr int NP = decltype(npc)::value;
+                return launch256(dcn_bwd_data_xn_kernel<NP, true>, dim3(a.ntiles, bwd_tap_groups(a)), bwd_xn_lds_bytes(NP, a.kh * a.kw * a.dg), st, a);
+            }))
+            return rc;
+        break;
+    }
+    pl.ga.raw = pl.aa.raw = r.data != GATHER_XN ? 1 : 0;
     pl.ga.Hb = pl.aa.Hb = Hb;
     pl.ga.gcol = a.gcol, pl.ga.start = start, pl.ga.ent = ent;
     if (pl.aa.ng > 0) {   // per-anchor sums of all four corners, then four of them per pixel
@@ -863,53 +953,20 @@ static int launch_bwd_colbuf(DcnArgs &a, GatherPlan &pl, unsigned char *ws, hipS
     return 0;
 }
 
-// gather_ws: device scratch of >= the plan's byte count for the atomic-free path, or NULL
-static int launch_bwd_data(DcnArgs &a, void *gather_ws, size_t gather_ws_bytes, hipStream_t st)
+// gather_ws: the scratch the route's plan was sized for (GATHER_* only)
+static int launch_bwd_data(DcnArgs &a, DcnRoute &r, void *gather_ws, hipStream_t st)
 {
     ProfScope prof(PROF_BWD_DATA, a, st);
-    const int np = math_np();
-    if ((a.mm || bwd_x3_ok(a) || bwd_grouped_ok(a)) && gather_ws && bwd_colbuf_env()) {
-        GatherPlan pl;
-        gather_plan(a, pl);
-        if (pl.ok && pl.bytes <= gather_ws_bytes) {
-            unsigned char *ws = reinterpret_cast<unsigned char *>(gather_ws);
-            switch (np) {
-            case 0: return launch_bwd_colbuf<0>(a, pl, ws, st);
-            case 1: return launch_bwd_colbuf<1>(a, pl, ws, st);
-            case 3: return launch_bwd_colbuf<3>(a, pl, ws, st);
-            case 6: return launch_bwd_colbuf<6>(a, pl, ws, st);
-            default: return fail(LSN_ERR_INVALID, "deformable backward: unknown math mode (%d products)", np);
-            }
-        }
-    }
-    if (a.mm) return fail(LSN_ERR_RUNTIME, "deformable backward: fragment-order weights without the gather path");
-    a.gcol = nullptr, a.gtap = nullptr;
+    if (r.gather()) return launch_bwd_gather(a, r, reinterpret_cast<unsigned char *>(gather_ws), st);
     for (int i = 0; i < a.nlv; ++i)   // the scatter kernels accumulate: start from zero (once per buffer is enough)
         if (a.lv[i].gx)
             LSN_HIP(hipMemsetAsync(a.lv[i].gx, 0, sizeof(float) * (size_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C, st));
-    if (bwd_x3_ok(a)) {
-        const size_t lds = bwd_xn_lds_bytes(np, a.kh * a.kw * a.dg);
-        auto gox = [&](auto kern) -> int {
-            if (int rc = set_lds(kern, lds)) return rc;
-            hipLaunchKernelGGL(kern, dim3(a.ntiles, bwd_tap_groups(a)), dim3(256), lds, st, a);
-            LSN_HIP(hipGetLastError());
-            return 0;
-        };
-        return split_dispatch(np, [&](auto npc) { return gox(dcn_bwd_data_xn_kernel<decltype(npc)::value, false>); });
-    }
+    if (r.data == SCATTER_XN)
+        return split_dispatch(math_np(), [&](auto npc) {
+            constexpr int NP = decltype(npc)::value;
+            return launch256(dcn_bwd_data_xn_kernel<NP, false>, dim3(a.ntiles, bwd_tap_groups(a)), bwd_xn_lds_bytes(NP, a.kh * a.kw * a.dg), st, a);
+        });
     return (a.Co / a.groups > 64) ? launch_bwd_data_t<256>(a, st) : launch_bwd_data_t<64>(a, st);
-}
-
-// Pixel splits of a weight-gradient launch: the grid (columns x splits x co blocks) fills ONE round of the blocks the chip
-// holds at once (256 CUs x per_cu), rounded DOWN.  Measured on the benchmark step (profiles/r2_wgrad_rounds.txt): the
-// old cdiv(1024, 36) = 29 splits made 1044 blocks = two full rounds plus a third with 20 blocks (0.88 ms per DCN
-// launch); 28 splits 0.68 ms; one round instead of two is the same for the DCN launches and 1.1 ms / step faster over
-// the dense layers (half the fp32 atomics of the epilogues).
-static int wgrad_splits(int cols, int per_cu)
-{
-    const int slots = 256 * per_cu;
-    int s = slots / cols;
-    return s < 1 ? 1 : s;
 }
 
 // 8-byte buffer loads in the split weight-gradient kernel: even channel counts, 8-byte aligned tensors, byte offsets < 2^31
@@ -930,13 +987,6 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
 bool conv_wgrad_fold_pending();   // conv.hip: lsn_conv2d_backward_weight_bn is the caller
 int conv_scratch(size_t floats, float **p, hipStream_t st);
 
-static bool mm_wgrad_ok(const DcnArgs &a)
-{
-    if (!mm_common_ok(a) || a.Co % 256 != 0 || (a.C / a.dg) % 64 != 0) return false;
-    if (a.gtap == nullptr || (reinterpret_cast<uintptr_t>(a.gtap) & 15) != 0) return false;
-    return true;
-}
-
 // dense: a dense convolution's weight gradient (levels without offsets, no backward-data pass before this one): the
 // sampling table is built here, and the launch is accounted to the caller's family
 static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hipStream_t st, bool dense = false)
@@ -944,8 +994,7 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
     DcnArgs a = a_in;
     const int K = a.kh * a.kw, npl = mm_npl();
     const size_t nW = (size_t)a.Co * K * a.C;
-    const size_t img_bytes = (size_t)nchunks * 2 * (a.Co / 32) * npl * 1024;
-    if (img_bytes >= ((size_t)1 << 31)) return 1;
+    const size_t img_bytes = (size_t)nchunks * 2 * (a.Co / 32) * npl * 1024;   // (< 2^31: wgrad_mm_image_ok)
     const int ncol = K * (a.C / 64), nz = a.Co / 256;
     int S = (512 + ncol * nz / 2) / (ncol * nz);
     if (S > nchunks / 4) S = nchunks / 4;   // a split should run long enough to amortise its prologue and its partial tile
@@ -957,15 +1006,9 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
     const size_t img_f = (img_bytes + 15) / 16 * 4, part_f = (size_t)S * nW, pb_f = ((size_t)nblk_s * a.Co + 3) & ~(size_t)3;
     const size_t meta_f = ((size_t)nchunks * 8 + 64 + 3) & ~(size_t)3;
     size_t tap_entries = 0;
-    if (dense) {
-        int64_t rows = 0;
-        for (int i = 0; i < a.nlv; ++i) {
-            a.lv[i].prow0 = (int)rows;
-            rows += a.lv[i].P;
-        }
-        if (rows * K * a.dg >= ((int64_t)1 << 26)) return 1;   // (a 2 GB table)
-        a.gtap_rows = (int)rows;
-        tap_entries = (size_t)rows * K * a.dg;
+    if (dense) {   // (< 2^26 entries, a 2 GB table: conv_wgrad_dense_mm_ok)
+        a.gtap_rows = number_rows(a);
+        tap_entries = (size_t)a.gtap_rows * K * a.dg;
     }
     float *base = nullptr;
     if (int rc = conv_scratch(img_f + part_f + pb_f + meta_f + (tap_entries ? (tap_entries + 1) * (sizeof(Tap) / 4) : 0), &base, st))
@@ -991,59 +1034,37 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
     const size_t lds = dcn_wgrad_mm_lds_bytes(npl);
     if ((long long)nchunks * (S + 1) >= (1ll << 32))
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward-weight: %d chunks x %d splits exceed the kernel's 32-bit split arithmetic", nchunks, S);
-    auto go = [&](auto kern) -> int {
-        if (int rc = set_lds(kern, lds)) return rc;
-        hipLaunchKernelGGL(kern, dim3(ncol, S, nz), dim3(256), lds, st, a, nchunks, img, (int)img_bytes, part, meta);
-        LSN_HIP(hipGetLastError());
-        return 0;
-    };
     // (FINE = the fine MFMA / staging interleave: tower 360 -> 345 us, pyramid 941 -> 916 us, profiles/r4_fine.txt)
     if (int rc = split_dispatch(math_np(), [&](auto np) {
             constexpr int NP = decltype(np)::value;
-            return dense ? go(dcn_wgrad_mm_kernel<NP, true, true>) : go(dcn_wgrad_mm_kernel<NP, false, true>);
+            const dim3 grid(ncol, S, nz);
+            return dense ? launch256(dcn_wgrad_mm_kernel<NP, true, true>, grid, lds, st, a, nchunks, img, (int)img_bytes, part, meta)
+                         : launch256(dcn_wgrad_mm_kernel<NP, false, true>, grid, lds, st, a, nchunks, img, (int)img_bytes, part, meta);
         }))
         return rc;
     return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, S, nblk_s, accumulate ? 1 : 0, st);
-}
-
-static bool grouped_wgrad_ok(const DcnArgs &a)
-{
-    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C || a.kh * a.kw > 9) return false;
-    const int cg = a.C / a.groups;
-    if (!(cg == 4 || cg == 8 || cg == 16 || cg == 32) || ((int64_t)a.C * cg) % 256 != 0 || a.C % a.dg != 0) return false;
-    const int nch = cg >= 16 ? cg : 256 / cg;
-    if ((a.C / a.dg) % nch != 0 || a.C % nch != 0) return false;
-    for (int i = 0; i < a.nlv; ++i)
-        if ((int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(a.lv[i].x) & 15) != 0)
-            return false;
-    return true;
 }
 
 // grouped weight gradient (dcn_grouped_kernels.h): pixel splits leave partial tiles, the ordered reduce adds them (or queues)
 static int launch_wgrad_grouped(const DcnArgs &a_in, bool accumulate, hipStream_t st)
 {
     DcnArgs a = a_in;
-    int64_t rows = 0;
-    for (int i = 0; i < a.nlv; ++i) {
-        a.lv[i].prow0 = (int)rows;      // (the numbering of the backward-data pass's table, when there is one)
-        rows += a.lv[i].P;
-    }
-    if (rows >= ((int64_t)1 << 30)) return 1;
-    if ((reinterpret_cast<uintptr_t>(a.gtap) & 15) != 0 || a.gtap_rows != (int)rows) a.gtap = nullptr;
+    const int rows = number_rows(a);   // (the numbering of the backward-data pass's table, when there is one; < 2^30: route_backward)
+    if ((reinterpret_cast<uintptr_t>(a.gtap) & 15) != 0 || a.gtap_rows != rows) a.gtap = nullptr;
     const int K = a.kh * a.kw, cg = a.C / a.groups;
     const int ny = (int)((int64_t)a.C * cg / 256);
     const int nch = cg >= 16 ? cg : 256 / cg, nco = 256 / cg;
     int splits = cdiv(3072, ny);                               // ~12 workgroups per CU: the kernel lives on loads in flight
-    int per = cdiv((int)rows, splits);
+    int per = cdiv(rows, splits);
     per = cdiv(per, GRP_PB) * GRP_PB;
     if (per < 4 * GRP_PB) per = 4 * GRP_PB;
-    splits = cdiv((int)rows, per);
+    splits = cdiv(rows, per);
     const size_t nW = (size_t)a.Co * K * cg;
     const size_t cap = ((size_t)256 << 20) / 4 / (nW + a.Co);  // partial tiles: at most 256 MB
     if ((size_t)splits > cap) {
         splits = (int)(cap > 0 ? cap : 1);
-        per = cdiv(cdiv((int)rows, splits), GRP_PB) * GRP_PB;
-        splits = cdiv((int)rows, per);
+        per = cdiv(cdiv(rows, splits), GRP_PB) * GRP_PB;
+        splits = cdiv(rows, per);
     }
     float *base = nullptr;
     if (int rc = conv_scratch((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
@@ -1051,50 +1072,29 @@ static int launch_wgrad_grouped(const DcnArgs &a_in, bool accumulate, hipStream_
     ProfScope prof(PROF_WGRAD, a, st);
     const size_t lds = dcn_wgrad_grouped_lds_bytes(K, nch, nco);
     const dim3 grid(splits, ny);
-    auto go = [&](auto kern) -> int {
-        if (int rc = set_lds(kern, lds)) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a, (int)rows, per, part, part_b);
-        LSN_HIP(hipGetLastError());
-        return 0;
-    };
     int rc;
     switch (cg) {
-    case 4: rc = go(dcn_wgrad_grouped_kernel<4, 9>); break;
-    case 8: rc = go(dcn_wgrad_grouped_kernel<8, 9>); break;
-    case 16: rc = go(dcn_wgrad_grouped_kernel<16, 9>); break;
-    default: rc = go(dcn_wgrad_grouped_kernel<32, 9>); break;
+    case 4: rc = launch256(dcn_wgrad_grouped_kernel<4, 9>, grid, lds, st, a, rows, per, part, part_b); break;
+    case 8: rc = launch256(dcn_wgrad_grouped_kernel<8, 9>, grid, lds, st, a, rows, per, part, part_b); break;
+    case 16: rc = launch256(dcn_wgrad_grouped_kernel<16, 9>, grid, lds, st, a, rows, per, part, part_b); break;
+    default: rc = launch256(dcn_wgrad_grouped_kernel<32, 9>, grid, lds, st, a, rows, per, part, part_b); break;
     }
     if (rc) return rc;
     return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
 }
 
-static int launch_wgrad(const DcnArgs &a_in, int nsteps, bool accumulate, hipStream_t st)
+// the split kernels (WG_XN_* / WG_FP32_*): ORDERED = one partial gradient per pixel split + an ordered reduce; a block that
+// runs no step still stores its zero tile, so every partial element is written.  ATOMIC: fp32 atomics into the gradient.
+static int launch_wgrad_split(const DcnArgs &a_in, const DcnRoute &r, bool accumulate, hipStream_t st)
 {
-    if (grouped_wgrad_ok(a_in) && a_in.opitch == a_in.Co && ((size_t)a_in.Co * a_in.kh * a_in.kw * (a_in.C / a_in.groups)) % 4 == 0) {
-        const int rc = launch_wgrad_grouped(a_in, accumulate, st);
-        if (rc != 1) return rc;
-    }
-    if (mm_wgrad_ok(a_in)) {
-        const int rc = launch_wgrad_mm(a_in, nsteps, accumulate, st);
-        if (rc != 1) return rc;   // 1: not served (sizes), fall through
-    }
-    if (a_in.opitch != a_in.Co)
-        return fail(LSN_ERR_UNSUPPORTED, "deformable weight gradient: out_pitch outside the fragment-order kernel");
     DcnArgs a = a_in;
     a.wg_vec = wgrad_vec_bits(a);
     if ((reinterpret_cast<uintptr_t>(a.gtap) & 15) != 0) a.gtap = nullptr;
-    const int K = a.kh * a.kw, Cg = a.C / a.groups, Cog = a.Co / a.groups;
-    const int segs = Cg / a.SL, ncc = cdiv(a.SL, WG_BN);
-    const int ncol = a.groups * K * segs * ncc, nz = cdiv(Cog, WG_BM);
-    int splits = wgrad_splits(ncol * nz, 2);   // 2 resident blocks per CU (246 VGPRs, 78 KB LDS)
-    if (splits > nsteps) splits = nsteps;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    const size_t lds = (size_t)WG_BP * (WG_BM + WG_BN) * 4 + 2 * WG_BP * sizeof(Tap);
-    // split-bf16 kernels: one partial gradient per pixel split + an ordered reduce instead of fp32 atomics (deterministic);
-    // a block that runs no step still stores its zero tile, so every partial element is written
-    const size_t nW = (size_t)a.Co * K * Cg;
-    const bool ordered = nW % 4 == 0 && (size_t)splits * (nW + a.Co) * sizeof(float) <= ((size_t)256 << 20);
+    const int nsteps = r.wg_steps;
+    int ncol, nz;
+    const int splits = wgrad_split_grid(a, nsteps, &ncol, &nz);
+    const size_t nW = (size_t)a.Co * a.kh * a.kw * (a.C / a.groups);
+    const bool ordered = r.wgrad == WG_XN_ORDERED || r.wgrad == WG_FP32_ORDERED;
     if (ordered) {
         float *base = nullptr;
         if (int rc = conv_scratch((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
@@ -1105,35 +1105,64 @@ static int launch_wgrad(const DcnArgs &a_in, int nsteps, bool accumulate, hipStr
         if (a.gb) LSN_HIP(hipMemsetAsync(a.gb, 0, sizeof(float) * (size_t)a.Co, st));
     }
     ProfScope prof(PROF_WGRAD, a, st);
-    if (ordered && math_np() == 0) {   // exact fp32 (fp32 MFMA), partial gradients per split: deterministic
-        if (vec_ok(a))
-            hipLaunchKernelGGL(dcn_wgrad_kernel<true>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
-        else
-            hipLaunchKernelGGL(dcn_wgrad_kernel<false>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
-        LSN_HIP(hipGetLastError());
-        return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
+    const dim3 grid(ncol, splits, nz);
+    int rc;
+    if (r.wgrad == WG_FP32_ORDERED || r.wgrad == WG_FP32_ATOMIC) {   // exact fp32 (fp32 MFMA)
+        const size_t lds = (size_t)WG_BP * (WG_BM + WG_BN) * 4 + 2 * WG_BP * sizeof(Tap);
+        rc = vec_ok(a) ? launch256(dcn_wgrad_kernel<true>, grid, lds, st, a, nsteps) : launch256(dcn_wgrad_kernel<false>, grid, lds, st, a, nsteps);
+    } else {
+        rc = split_dispatch(math_np(), [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            return launch256(dcn_wgrad_xn_kernel<false, NP>, grid, wgrad_xn_lds_bytes<NP>(), st, a, nsteps);
+        });
     }
-    auto go_xn = [&](auto np) -> int {
-        constexpr int NP = decltype(np)::value;
-        const size_t ldsn = wgrad_xn_lds_bytes<NP>();
-        if (int rc = set_lds(dcn_wgrad_xn_kernel<false, NP>, ldsn)) return rc;
-        hipLaunchKernelGGL((dcn_wgrad_xn_kernel<false, NP>), dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
-        LSN_HIP(hipGetLastError());
-        return 0;
-    };
-    if (ordered) {
-        if (int rc = split_dispatch(math_np(), go_xn)) return rc;
-        return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
+    if (rc || !ordered) return rc;
+    return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
+}
+
+static int launch_wgrad(const DcnArgs &a, const DcnRoute &r, bool accumulate, hipStream_t st)
+{
+    DcnArgs w = a;   // same levels, step (32-pixel) indexing
+    number_tiles(w, WG_BP);
+    switch (r.wgrad) {
+    case WG_GROUPED: return launch_wgrad_grouped(w, accumulate, st);
+    case WG_MM: return launch_wgrad_mm(w, r.wg_steps, accumulate, st);
+    default: return launch_wgrad_split(w, r, accumulate, st);
     }
-    if (math_np()) return split_dispatch(math_np(), go_xn);
-    if (vec_ok(a))
-        hipLaunchKernelGGL(dcn_wgrad_kernel<true>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
-    else
-        hipLaunchKernelGGL(dcn_wgrad_kernel<false>, dim3(ncol, splits, nz), dim3(256), lds, st, a, nsteps);
+}
+
+// The weight image the route names, into the caller's `workspace`.  IMG_FRAGMENT: fragment order (forward: (Co, K, C) as it
+// lies; backward: the transposed 1x1 view with N = K * C columns and the reduction over Co), already there with
+// weights_prepared.  IMG_PLANES / IMG_PLANES_T: the split bf16 planes of dcn_kernels.h.
+static int prepare_image(DcnArgs &a, WeightImage image, const lsn_dcn_shape &s, bool backward, hipStream_t st)
+{
+    if (image == IMG_NONE) return 0;
+    unsigned short *dst = reinterpret_cast<unsigned short *>(s.workspace);
+    const int K = a.kh * a.kw, np = math_np();
+    WfragJob j = {};
+    TapSub ts = {0, 1, 1, 0, 1, 1, 1};
+    j.w = a.w, j.out = dst, j.Co = backward ? K * a.C : a.Co, j.K = backward ? 1 : K, j.C = backward ? a.Co : a.C;
+    j.flipT = backward ? 1 : 0, j.ts = ts;
+    const long long total = wfrag_threads(j);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    if (int rc = split_dispatch(np, [&](auto npc) {
+            constexpr int NPL = SplitCfg<decltype(npc)::value>::NPL;
+            if (image == IMG_PLANES)
+                hipLaunchKernelGGL(dcn_prepare_w_kernel<NPL>, dim3(512), dim3(256), 0, st, a.w, dst, (size_t)a.Co * K * (a.C / a.groups));
+            else if (image == IMG_PLANES_T)
+                hipLaunchKernelGGL(dcn_prepare_wt_kernel<NPL>, dim3(512), dim3(256), 0, st, a.w, dst, a.Co, K, a.C);
+            else if (!s.weights_prepared)
+                hipLaunchKernelGGL(conv_wfrag_kernel<NPL>, dim3(blocks), dim3(256), 0, st, j);
+            return 0;
+        }))
+        return rc;
     LSN_HIP(hipGetLastError());
+    a.wtp = dst;
+    if (image == IMG_FRAGMENT) a.wtp_bytes = (int)cv_wfrag_bytes(j.Co, j.K, j.C, mm_npl());
     return 0;
 }
 
+static size_t gather_ws_bytes(const lsn_dcn_shape &s) { return (size_t)(s.gather_workspace_bytes > 0 ? s.gather_workspace_bytes : 0); }
 static size_t n_in(const lsn_dcn_shape &s, const lsn_dcn_level &d) { return (size_t)d.B * s.C * d.H * d.W; }
 static size_t n_out(const lsn_dcn_shape &s, const lsn_dcn_level &d) { return (size_t)d.B * s.Co * d.Ho * d.Wo; }
 
@@ -1170,25 +1199,22 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
         }
     }
     a.bias = bias;
-    a.wtp = nullptr;
-    if (a.opitch != a.Co && !(layout == LSN_NHWC && s.workspace && mm_fwd_ok(a)))
+    const DcnRoute r = route_forward(a, s, layout);
+    if (a.opitch != a.Co && !r.pitched)
         return fail(LSN_ERR_UNSUPPORTED, "deformable forward: out_pitch %d != Co %d outside the matrix-pipe kernels "
                     "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
-    if (s.weights_prepared && !(layout == LSN_NHWC && s.workspace && mm_fwd_ok(a)))
+    if (s.weights_prepared && !r.prepared)
         return fail(LSN_ERR_UNSUPPORTED, "deformable forward: weights_prepared outside the matrix-pipe kernels (lsn_dcn_prepared_ok)");
-    if (s.workspace && mm_fwd_ok(a)) {
-        if (int rc = mm_prepare_weights(a, false, s.workspace, st, s.weights_prepared != 0)) return rc;
-    } else if (s.workspace && math_np() && (Cg % 8 == 0) && a.Co / a.groups > 64 && xn_ok(a)) {
-        const size_t nw = (size_t)s.Co * K * Cg;   // split the weights once instead of in every block
-        if (int rc = split_dispatch(math_np(), [&](auto np) {
-                hipLaunchKernelGGL(dcn_prepare_w_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(512), dim3(256), 0, st, a.w,
-                                   reinterpret_cast<unsigned short *>(s.workspace), nw);
-                return 0;
-            }))
-            return rc;
-        a.wtp = reinterpret_cast<const unsigned short *>(s.workspace);
+    if (int rc = prepare_image(a, r.image, s, false, st)) return rc;
+    int rc = 0;
+    switch (r.fwd) {
+    case FWD_MM: rc = launch_forward_mm(a, st); break;
+    case FWD_GROUPED: rc = launch_forward_grouped(a, st); break;
+    case FWD_XN_PLANES: rc = launch_forward_xn(a, true, st); break;
+    case FWD_XN: rc = launch_forward_xn(a, false, st); break;
+    case FWD_FP32: rc = launch_forward_fp32(a, st); break;
     }
-    if (int rc = launch_forward(a, st)) return rc;
+    if (rc) return rc;
     if (layout == LSN_NCHW)
         for (int i = 0; i < n; ++i)
             if (int rc = permute_rs(out_tmp[i], lv[i].output, lv[i].B, lv[i].Ho * lv[i].Wo, s.Co, st)) return rc;
@@ -1208,11 +1234,7 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     const int K = s.kh * s.kw, Cg = s.C / s.groups;
     std::vector<float *> gx_tmp(n, nullptr);
     float *gw_tmp = nullptr;
-    bool any_data = false;
-    for (int i = 0; i < n; ++i) {
-        LSN_CHECK(lv[i].input && lv[i].grad_output, "level %d: input/grad_output is NULL", i);
-        any_data = any_data || lv[i].grad_input || lv[i].grad_offset || lv[i].grad_mask;
-    }
+    for (int i = 0; i < n; ++i) LSN_CHECK(lv[i].input && lv[i].grad_output, "level %d: input/grad_output is NULL", i);
     if (layout == LSN_NHWC) {
         a.w = weight;
         a.gw = grad_weight;
@@ -1247,55 +1269,24 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     }
     a.gb = grad_bias;
 
-    if (any_data) {
-        a.wtp = nullptr;
-        a.gcol = nullptr;
-        const bool can_split = s.workspace && math_np() && s.groups == 1 && s.Co % 2 == 0;
-        if (can_split) a.wtp = reinterpret_cast<const unsigned short *>(s.workspace);   // (format: decided below)
-        void *gws = s.gather_workspace;
-        size_t gws_bytes = (size_t)(s.gather_workspace_bytes > 0 ? s.gather_workspace_bytes : 0);
-        if (!gws && layout == LSN_NCHW && (a.wtp || bwd_grouped_ok(a)) && bwd_colbuf_env()) {   // reference-layout entry points: own scratch
-            GatherPlan pl;
-            DcnArgs probe = a;
-            gather_plan(probe, pl);
-            if (pl.ok && (gws = ws.get(pl.bytes / 4 + 64)) != nullptr) gws_bytes = pl.bytes;
-        }
-        bool mm = false;   // the GEMM of dcn_mm_kernels.h: only together with the gather pass
-        if (can_split && gws && bwd_colbuf_env() && mm_bwd_ok(a) && bwd_gather_ok(a)) {
-            GatherPlan pl;
-            DcnArgs probe = a;
-            gather_plan(probe, pl);
-            mm = pl.ok && pl.bytes <= gws_bytes;
-        }
-        if (a.opitch != a.Co && !(mm && layout == LSN_NHWC))
-            return fail(LSN_ERR_UNSUPPORTED, "deformable backward: out_pitch %d != Co %d outside the matrix-pipe kernels "
-                        "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
-        if (s.weights_prepared && !(mm && layout == LSN_NHWC))
-            return fail(LSN_ERR_UNSUPPORTED, "deformable backward: weights_prepared outside the matrix-pipe kernels (lsn_dcn_prepared_ok)");
-        if (mm) {
-            if (int rc = mm_prepare_weights(a, true, s.workspace, st, s.weights_prepared != 0)) return rc;
-        } else if (can_split) {
-            if (int rc = split_dispatch(math_np(), [&](auto np) {
-                    hipLaunchKernelGGL(dcn_prepare_wt_kernel<SplitCfg<decltype(np)::value>::NPL>, dim3(512), dim3(256), 0, st, a.w,
-                                       reinterpret_cast<unsigned short *>(s.workspace), s.Co, K, s.C);
-                    return 0;
-                }))
-                return rc;
-        }
-        if (int rc = launch_bwd_data(a, gws, gws_bytes, st)) return rc;
-    } else if (a.opitch != a.Co) {
+    void *gws = s.gather_workspace;
+    DcnRoute r = route_backward(a, s, layout, gws, gather_ws_bytes(s), a.gw != nullptr);
+    if (a.opitch != a.Co && r.data == DATA_NONE)
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward: out_pitch without a data-gradient pass");
+    if (a.opitch != a.Co && !r.pitched)
+        return fail(LSN_ERR_UNSUPPORTED, "deformable backward: out_pitch %d != Co %d outside the matrix-pipe kernels "
+                    "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
+    if (s.weights_prepared && r.data != DATA_NONE && !r.prepared)
+        return fail(LSN_ERR_UNSUPPORTED, "deformable backward: weights_prepared outside the matrix-pipe kernels (lsn_dcn_prepared_ok)");
+    if (r.data != DATA_NONE) {
+        if (r.own_gather_ws && !(gws = ws.get(r.plan.bytes / 4 + 64)))   // reference-layout entry points: own scratch
+            return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
+        if (int rc = prepare_image(a, r.image, s, true, st)) return rc;
+        if (int rc = launch_bwd_data(a, r, gws, st)) return rc;
     }
-    if (a.gw) {
-        DcnArgs w = a;  // same levels, step (32-pixel) indexing
-        int steps = 0;
-        for (int i = 0; i < n; ++i) {
-            w.lv[i].tile0 = steps;
-            steps += cdiv(w.lv[i].P, WG_BP);
-        }
-        // (the reference-layout path computes into a temporary that is permuted into grad_weight: no accumulation there)
-        if (int rc = launch_wgrad(w, steps, s.accumulate_param_grads != 0 && layout == LSN_NHWC, st)) return rc;
-    }
+    // (the reference-layout path computes into a temporary that is permuted into grad_weight: no accumulation there)
+    if (r.wgrad != WG_NONE)
+        if (int rc = launch_wgrad(a, r, s.accumulate_param_grads != 0 && layout == LSN_NHWC, st)) return rc;
     if (layout == LSN_NCHW) {
         for (int i = 0; i < n; ++i)
             if (gx_tmp[i])
@@ -1378,11 +1369,7 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
         LSN_HIP(hipMemsetAsync(a.gw, 0, sizeof(float) * nW, st));
         if (a.gb) LSN_HIP(hipMemsetAsync(a.gb, 0, sizeof(float) * (size_t)Co, st));
     }
-    const size_t ldsn = wgrad_xn_lds_bytes<NP, BMW>();
-    auto k = dcn_wgrad_xn_kernel<true, NP, BMW>;
-    if (int rc = set_lds(k, ldsn)) return rc;
-    hipLaunchKernelGGL(k, dim3(ncol, splits, nz), dim3(256), ldsn, st, a, nsteps);
-    LSN_HIP(hipGetLastError());
+    if (int rc = launch256(dcn_wgrad_xn_kernel<true, NP, BMW>, dim3(ncol, splits, nz), wgrad_xn_lds_bytes<NP, BMW>(), st, a, nsteps)) return rc;
     if (ordered) return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, Co, splits, splits, accumulate ? 1 : 0, st);
     return 0;
 }
@@ -1390,95 +1377,86 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
 int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
                   int dil, int accumulate, hipStream_t st);   // conv.hip
 
-// The weight gradient of a dense convolution through dcn_wgrad_mm_kernel<NP, DENSE> (grad_output pre-split once into MFMA
-// fragment order, the regular grid as the sampling table).  Returns 1 when the shape is not served (256 | Co, 64 | C,
-// 32-bit byte offsets, a split-bf16 math mode) or is faster on the patch kernel of conv_wgrad_kernels.h.  Measured on the
-// layer shapes of the benchmark step (tools/ubench/wgrad_ab.hip, profiles/r3_wgrad_ab.txt; batch 2): 3x3 at >= 4096
-// output pixels 84 vs 96 us (layer 3), 262 vs 272 (FPN P3), 320 vs 380 (five head levels in one launch); 1x1 from >= 1024
-// channels to >= 512: 75 vs 89, 53 vs 56; strided 1x1 from >= 512 channels: 83 vs 89, 78 vs 89.  Slower on the 1x1 layers
-// with few input channels and many pixels (76 vs 52 us on 128 -> 512 at 100 x 168), which stay where they were.
-static int conv_wgrad_dense_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
-                               int pad, int dil, bool accumulate, hipStream_t st)
+// The levels of a dense convolution as DcnArgs (no offsets: the regular grid is the sampling table), 32-pixel steps in *steps
+static int conv_levels(DcnArgs &a, int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
+                       int pad, int dil, int *steps)
 {
-    if (n < 1 || n > MAXLV || !lv || !gw || Co % 256 != 0 || C % 64 != 0) return 1;
-    int64_t opx = 0;   // output pixels
-    for (int i = 0; i < n; ++i) {
-        const int Ho = (lv[i].H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (lv[i].W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
-        opx += (int64_t)lv[i].B * (Ho > 0 ? Ho : 0) * (Wo > 0 ? Wo : 0);
-    }
-    // (all of them measured at >= 2100 output pixels; smaller launches stay where they were)
-    const bool win = kh * kw >= 9 ? opx >= 4096 : opx >= 2048 && ((C >= 1024 && Co >= 512) || (stride >= 2 && C >= 512));
-    if (!win) return 1;
-    DcnArgs a = {};
-    int chunks = 0;
-    for (int i = 0; i < n; ++i) {
-        Lvl &L = a.lv[i];
-        const int B = lv[i].B, H = lv[i].H, W = lv[i].W;
-        if (!lv[i].x || !lv[i].grad_out || B <= 0 || H <= 0 || W <= 0) return 1;
-        if (((reinterpret_cast<uintptr_t>(lv[i].x) | reinterpret_cast<uintptr_t>(lv[i].grad_out)) & 15) != 0) return 1;   // 16-byte loads
-        const int Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
-        if (Ho <= 0 || Wo <= 0) return 1;
-        if ((int64_t)B * H * W * C * 4 >= ((int64_t)1 << 31) || (int64_t)B * Ho * Wo * Co * 4 >= ((int64_t)1 << 31)) return 1;
-        L.x = lv[i].x, L.gout = lv[i].grad_out, L.off = nullptr, L.msk = nullptr;
-        L.B = B, L.H = H, L.W = W, L.Ho = Ho, L.Wo = Wo, L.P = B * Ho * Wo, L.sh = L.sw = 1.f;
-        L.tile0 = chunks;
-        chunks += cdiv(L.P, WG_BP);
-    }
-    a.nlv = n;
-    a.C = C, a.Co = Co, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.dil = dil, a.groups = 1, a.dg = 1;
-    a.SL = C;
-    a.opitch = Co;
-    a.gw = gw, a.gb = gb;
-    if (!mm_common_ok(a) || chunks < 8) return 1;
-    double px = 0, in_el = 0;
-    for (int i = 0; i < n; ++i) px += (double)a.lv[i].P, in_el += (double)a.lv[i].B * a.lv[i].H * a.lv[i].W * C;
-    ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * Co * C * kh * kw, 4.0 * (in_el + px * Co + (double)Co * kh * kw * C), st);
-    return launch_wgrad_mm(a, chunks, accumulate, st, true);
-}
-
-static int conv_wgrad_xn(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
-                         int pad, int dil, bool accumulate, hipStream_t st)
-{
-    {   // wide layers: the fragment-order kernel of the deformable family with the regular grid as its sampling table
-        const int rc = conv_wgrad_dense_mm(n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, accumulate, st);
-        if (rc != 1) return rc;
-    }
-    {   // the patch kernel of conv_wgrad_kernels.h serves up to nine taps; anything else stays here
-        const int rc = conv_wgrad_mm(n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, accumulate ? 1 : 0, st);
-        if (rc != 1) return rc;
-    }
     LSN_CHECK(n >= 1 && n <= MAXLV && lv && gw, "conv2d backward-weight: bad arguments");
-    DcnArgs a = {};
-    int steps = 0;
+    *steps = 0;
     for (int i = 0; i < n; ++i) {
         Lvl &L = a.lv[i];
         const int B = lv[i].B, H = lv[i].H, W = lv[i].W;
         LSN_CHECK(lv[i].x && lv[i].grad_out && B > 0 && H > 0 && W > 0, "conv2d backward-weight: bad level %d", i);
-        const int Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
+        const int Ho = conv_out(H, kh, stride, pad, dil), Wo = conv_out(W, kw, stride, pad, dil);
         LSN_CHECK(Ho > 0 && Wo > 0, "conv2d backward-weight: output size is too small");
-        if ((int64_t)B * H * W * C >= ((int64_t)1 << 31) || (int64_t)B * Ho * Wo * Co >= ((int64_t)1 << 31))
+        if (!fits_i32((int64_t)B * H * W * C) || !fits_i32((int64_t)B * Ho * Wo * Co))
             return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight: tensor too large for 32-bit indexing");
         L.x = lv[i].x, L.gout = lv[i].grad_out, L.off = nullptr, L.msk = nullptr;
         L.B = B, L.H = H, L.W = W, L.Ho = Ho, L.Wo = Wo, L.P = B * Ho * Wo, L.sh = L.sw = 1.f;
-        L.tile0 = steps;
-        steps += cdiv(L.P, WG_BP);
+        L.tile0 = *steps;
+        *steps += cdiv(L.P, WG_BP);
     }
     a.nlv = n;
     a.C = C, a.Co = Co, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.dil = dil, a.groups = 1, a.dg = 1;
     a.SL = C;
     a.opitch = Co;
     a.gw = gw, a.gb = gb;
-    a.wg_vec = wgrad_vec_bits(a);
-    const int K = kh * kw;
+    return 0;
+}
+
+static ProfSpan conv_wgrad_span(const DcnArgs &a, hipStream_t st)
+{
     double px = 0, in_el = 0;
-    for (int i = 0; i < n; ++i) px += (double)a.lv[i].P, in_el += (double)a.lv[i].B * a.lv[i].H * a.lv[i].W * C;
-    ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * Co * C * K, 4.0 * (in_el + px * Co + (double)Co * K * C), st);
+    for (int i = 0; i < a.nlv; ++i) px += (double)a.lv[i].P, in_el += (double)in_elems(a, i);
+    const double K = (double)a.kh * a.kw;
+    return ProfSpan(PROF_CONV_WGRAD, 2.0 * px * a.Co * a.C * K, 4.0 * (in_el + px * a.Co + a.Co * K * a.C), st);
+}
+
+// Whether the weight gradient of a dense convolution goes through dcn_wgrad_mm_kernel<NP, DENSE> (grad_output pre-split once
+// into MFMA fragment order, the regular grid as the sampling table): the shape is served (256 | Co, 64 | C, 16-byte aligned
+// tensors at 32-bit byte offsets, a split-bf16 math mode) and is not faster on the patch kernel of conv_wgrad_kernels.h.
+// Measured on the layer shapes of the benchmark step (tools/ubench/wgrad_ab.hip, profiles/r3_wgrad_ab.txt; batch 2): 3x3 at >= 4096
+// output pixels 84 vs 96 us (layer 3), 262 vs 272 (FPN P3), 320 vs 380 (five head levels in one launch); 1x1 from >= 1024
+// channels to >= 512: 75 vs 89, 53 vs 56; strided 1x1 from >= 512 channels: 83 vs 89, 78 vs 89.  Slower on the 1x1 layers
+// with few input channels and many pixels (76 vs 52 us on 128 -> 512 at 100 x 168), which stay where they were.
+static bool conv_wgrad_dense_mm_ok(const DcnArgs &a, int chunks)
+{
+    if (a.Co % 256 != 0 || a.C % 64 != 0) return false;
+    int64_t opx = 0;   // output pixels
+    for (int i = 0; i < a.nlv; ++i) {
+        opx += a.lv[i].P;
+        if (((reinterpret_cast<uintptr_t>(a.lv[i].x) | reinterpret_cast<uintptr_t>(a.lv[i].gout)) & 15) != 0) return false;   // 16-byte loads
+    }
+    // (all of them measured at >= 2100 output pixels; smaller launches stay where they were)
+    const bool win = a.kh * a.kw >= 9 ? opx >= 4096 : opx >= 2048 && ((a.C >= 1024 && a.Co >= 512) || (a.stride >= 2 && a.C >= 512));
+    if (!win || !mm_common_ok(a) || chunks < 8) return false;
+    return wgrad_mm_image_ok(a, chunks) && opx * a.kh * a.kw < ((int64_t)1 << 26);   // (the tap table: 2 GB)
+}
+
+// weight gradient of a dense convolution, summed over up to MAXLV input maps that share the weight
+static int conv_wgrad_xn(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
+                         int pad, int dil, bool accumulate, hipStream_t st)
+{
+    DcnArgs a = {};
+    int steps = 0;
+    const int bad = conv_levels(a, n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, &steps);
+    if (!bad && conv_wgrad_dense_mm_ok(a, steps)) {   // wide layers: the fragment-order kernel of the deformable family
+        ProfSpan prof = conv_wgrad_span(a, st);
+        return launch_wgrad_mm(a, steps, accumulate, st, true);
+    }
+    {   // the patch kernel of conv_wgrad_kernels.h serves up to nine taps (1: not served -- conv.hip); anything else stays here
+        const int rc = conv_wgrad_mm(n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, accumulate ? 1 : 0, st);
+        if (rc != 1) return rc;
+    }
+    if (bad) return bad;
+    a.wg_vec = wgrad_vec_bits(a);
+    ProfSpan prof = conv_wgrad_span(a, st);
     // exact-mode callers get the fp32-equivalent split: there is no fp32-MFMA dense wgrad
     const int np = math_np() == 0 ? 6 : math_np();
     return split_dispatch(np, [&](auto npc) {
         constexpr int NP = decltype(npc)::value;
-        return Co <= 64 ? conv_wgrad_launch<NP, 64>(a, steps, C, Co, K, accumulate, st)
-                        : conv_wgrad_launch<NP, 256>(a, steps, C, Co, K, accumulate, st);
+        return Co <= 64 ? conv_wgrad_launch<NP, 64>(a, steps, C, Co, kh * kw, accumulate, st)
+                        : conv_wgrad_launch<NP, 256>(a, steps, C, Co, kh * kw, accumulate, st);
     });
 }
 
@@ -1501,64 +1479,48 @@ int lsn_debug_phase_clocks(long long *device_buf_512, int word)
 }
 int lsn_version(void) { return 100; }
 
+// The queries: the arguments as a channels-last call binds them, then the route such a call would take
+static bool query_args(lsn::DcnArgs &a, const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
+{
+    using namespace lsn;
+    if (!shape || !levels || check_shape(*shape) != 0) return false;
+    if (fill_levels(a, *shape, n_levels, levels, backward ? BWD_BM : 64) != 0) return false;
+    for (int i = 0; i < n_levels; ++i) {
+        a.lv[i].x = levels[i].input;
+        a.lv[i].gout = levels[i].grad_output;
+        a.lv[i].gx = levels[i].grad_input;
+    }
+    return true;
+}
+
 int64_t lsn_dcn_backward_workspace_bytes(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels)
 {
     using namespace lsn;
-    if (!shape || !levels || !bwd_colbuf_env()) return 0;
-    if (check_shape(*shape) != 0) return 0;
     DcnArgs a;
-    if (fill_levels(a, *shape, n_levels, levels, BWD_BM) != 0) return 0;
-    for (int i = 0; i < n_levels; ++i) a.lv[i].gx = levels[i].grad_input, a.lv[i].goff = levels[i].grad_offset, a.lv[i].gmsk = levels[i].grad_mask;
-    a.wtp = reinterpret_cast<const unsigned short *>(shape);   // any non-NULL value: the caller passes `workspace` too
-    if (!bwd_gather_ok(a)) return 0;
-    GatherPlan pl;
-    gather_plan(a, pl);
-    return pl.ok ? (int64_t)pl.bytes : 0;
+    if (!query_args(a, shape, n_levels, levels, 1)) return 0;
+    lsn_dcn_shape s = *shape;
+    s.workspace = &s;   // any non-NULL value: the answer is for a call that passes `workspace` and a gather workspace of this size
+    const DcnRoute r = route_backward(a, s, LSN_NHWC, &s, SIZE_MAX, false);
+    return r.gather() ? (int64_t)r.plan.bytes : 0;
 }
 
 int lsn_dcn_prepared_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
 {
     using namespace lsn;
-    if (!shape || !levels || !shape->workspace || check_shape(*shape) != 0) return 0;
     DcnArgs a;
-    if (fill_levels(a, *shape, n_levels, levels, backward ? BWD_BM : 64) != 0) return 0;
-    if (!backward) return mm_fwd_ok(a) ? 1 : 0;
-    bool any_data = false;
-    for (int i = 0; i < n_levels; ++i) {
-        a.lv[i].gx = levels[i].grad_input, a.lv[i].goff = levels[i].grad_offset, a.lv[i].gmsk = levels[i].grad_mask;
-        any_data = any_data || levels[i].grad_input || levels[i].grad_offset || levels[i].grad_mask;
-    }
-    a.wtp = reinterpret_cast<const unsigned short *>(shape->workspace);
-    if (!any_data || !shape->gather_workspace || !bwd_colbuf_env() || math_np() == 0 || shape->groups != 1 || a.Co % 2 != 0) return 0;
-    if (!mm_bwd_ok(a) || !bwd_gather_ok(a)) return 0;
-    GatherPlan pl;
-    gather_plan(a, pl);
-    return (pl.ok && (int64_t)pl.bytes <= shape->gather_workspace_bytes) ? 1 : 0;
+    if (!query_args(a, shape, n_levels, levels, backward)) return 0;
+    if (!backward) return route_forward(a, *shape, LSN_NHWC).prepared ? 1 : 0;
+    return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), false).prepared ? 1 : 0;
 }
 
+// (backward: the answer is for a call that asks for grad_weight)
 int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
 {
     using namespace lsn;
-    if (!shape || !levels || !shape->workspace || check_shape(*shape) != 0) return 0;
     DcnArgs a;
-    if (fill_levels(a, *shape, n_levels, levels, backward ? BWD_BM : 64) != 0) return 0;
-    if (!backward) return mm_fwd_ok(a) ? 1 : 0;
-    bool any_data = false;
-    for (int i = 0; i < n_levels; ++i) {
-        a.lv[i].gx = levels[i].grad_input, a.lv[i].goff = levels[i].grad_offset, a.lv[i].gmsk = levels[i].grad_mask;
-        any_data = any_data || levels[i].grad_input || levels[i].grad_offset || levels[i].grad_mask;
-    }
-    a.wtp = reinterpret_cast<const unsigned short *>(shape->workspace);
-    if (!any_data || !shape->gather_workspace || !bwd_colbuf_env() || a.Co % 2 != 0) return 0;
-    if (!mm_bwd_ok(a) || !bwd_gather_ok(a)) return 0;
-    GatherPlan pl;
-    gather_plan(a, pl);
-    if (!pl.ok || (int64_t)pl.bytes > shape->gather_workspace_bytes) return 0;
-    // the weight gradient on the fragment-order kernel (launch_wgrad_mm)
-    if (a.Co % 256 != 0 || (a.C / a.dg) % 64 != 0) return 0;
-    int64_t steps = 0;
-    for (int i = 0; i < n_levels; ++i) steps += cdiv(a.lv[i].P, WG_BP);
-    return steps * 2 * (a.Co / 32) * mm_npl() * 1024 < ((int64_t)1 << 31) ? 1 : 0;
+    if (!query_args(a, shape, n_levels, levels, backward)) return 0;
+    if (!backward) return route_forward(a, *shape, LSN_NHWC).pitched ? 1 : 0;
+    return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), true).pitched ? 1 : 0;
 }
 
 int lsn_set_math_mode(int mode)

@@ -5,6 +5,7 @@ Tolerances: north_star asks for 1e-3 relative on fp32 conv/loss.  The default ar
 are run as well.  All of them are held to 1e-4 of the output range against the oracle (measured ~1e-6; the oracle's own
 fp32 summation order is part of that), and the default mode to 1e-6 against the exact-fp32 kernels
 (test_split6_matches_exact_fp32).  Index outputs (NMS keep) must be identical."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -184,6 +185,143 @@ def test_dcn_forward_backward(case, layout, dcn_kernel_choice):
         errs[n] = _report(case['name'] + '/' + n, gt, gref[n])
     print(case['name'], layout, {k: f'{v:.1e}' for k, v in errs.items()})
     assert all(e < TOL for e in errs.values()), errs
+
+
+QUERY_CHOICES = ['default', 'x6_first_gemms', 'math_fp32']
+LSN_ERR_UNSUPPORTED = -2
+
+
+def _dcn_query_answers(case, call=True):
+    """One channels-last level of `case`, shape / level / workspaces built as HipBackend builds them (workspace sizes from the
+    library's own answers).  Returns what the four queries said -- lsn_dcn_prepared_ok and lsn_dcn_pitched_ok, forward and
+    backward -- and, with `call`, asserts that the call each of them answers for does what the answer says: weights_prepared = 1
+    / out_pitch = 2 Co succeeds after a 1 and returns LSN_ERR_UNSUPPORTED after a 0 (for weights_prepared, naming the query)."""
+    from lsnet_amd.ops.conv import weight_image
+    from lsnet_amd.ops.hip_backend import HipBackend, _ptr, _stream, _strides
+    lib = _lib.load()
+    dev = _dev()
+    x, w, b, off, mask, go, cfg = _make(case, dev)
+    xd, wd, od, md, gd = (_to(t, dev, True) for t in (x, w, off, mask, go))
+    bd = None if b is None else b.to(dev)
+    B, Co, (Ho, Wo) = x.shape[0], w.shape[0], cfg['out_hw']
+    split = _lib.split_math()
+    answers = {}
+
+    def fresh():
+        shape = HipBackend._shape(wd, cfg)
+        levels = (_lib.DcnLevel * 1)()
+        L = levels[0]
+        L.input, L.offset, L.mask, L.off_st = _ptr(xd), _ptr(od), _ptr(md), _strides(od)
+        if md is not None:
+            L.mask_st = _strides(md)
+        L.B, L.H, L.W, L.Ho, L.Wo = B, x.shape[2], x.shape[3], Ho, Wo
+        L.scale_h, L.scale_w = cfg['sh'], cfg['sw']
+        return shape, levels, L
+
+    def verdict(name, q, rc, query_name=None):
+        err = lib.lsn_last_error().decode('utf-8', 'replace') if rc else ''
+        print(f"{case['name']} {name}: query {q}, call returned {rc} {err!r}")
+        answers[name] = q
+        if not call:
+            return
+        assert rc == (0 if q else LSN_ERR_UNSUPPORTED), (name, q, rc, err)
+        if rc and query_name:
+            assert query_name in err, (name, err)
+
+    cl = torch.channels_last
+    # ---- forward
+    ws = torch.empty(2 * wd.numel(), device=dev) if split else None             # pre-split weight planes / fragment image
+    plain = torch.empty((B, Co, Ho, Wo), device=dev, memory_format=cl)
+    shape, levels, L = fresh()
+    shape.workspace, L.output = _ptr(ws), _ptr(plain)
+    if call:
+        _lib.check(lib.lsn_dcn_forward(ctypes.byref(shape), 1, levels, _ptr(wd), _ptr(bd), 1, _stream()))
+    q = lib.lsn_dcn_prepared_ok(ctypes.byref(shape), 1, levels, 0)
+    out = torch.empty_like(plain)
+    L.output, shape.weights_prepared = _ptr(out), 1
+    if q:
+        img = weight_image(wd, 0, 1, cfg['pad'], cfg['dil'])
+        shape.workspace = _ptr(img)
+    rc = lib.lsn_dcn_forward(ctypes.byref(shape), 1, levels, _ptr(wd), _ptr(bd), 1, _stream()) if call else 0
+    verdict('prepared_fwd', q, rc, 'lsn_dcn_prepared_ok')
+    if q and call:   # (the same kernel on the same image: equal up to the order of the fp32 sums of a split tile)
+        assert _err(out, plain) < 1e-5
+    wide = torch.zeros((B, 2 * Co, Ho, Wo), device=dev).contiguous(memory_format=cl)   # the call writes the first Co channels of each pixel
+    shape, levels, L = fresh()
+    shape.workspace, L.output, shape.out_pitch = _ptr(ws), _ptr(wide), 2 * Co
+    q = lib.lsn_dcn_pitched_ok(ctypes.byref(shape), 1, levels, 0)
+    rc = lib.lsn_dcn_forward(ctypes.byref(shape), 1, levels, _ptr(wd), _ptr(bd), 1, _stream()) if call else 0
+    verdict('pitched_fwd', q, rc)
+    if q and call:
+        assert _err(wide[:, :Co], plain) < 1e-5 and not wide[:, Co:].any()
+    # ---- backward: every gradient
+    gx, goff = torch.empty_like(xd), torch.empty_like(od)
+    gmsk = None if md is None else torch.empty_like(md)
+    gw = torch.empty_like(wd)
+    gb = None if bd is None else torch.empty(Co, device=dev)
+    ws = torch.empty(2 * wd.numel(), device=dev) if (split and cfg['groups'] == 1) else None
+
+    def backward_args(gout):
+        shape, levels, L = fresh()
+        L.grad_output, L.grad_input, L.grad_offset, L.grad_mask = _ptr(gout), _ptr(gx), _ptr(goff), _ptr(gmsk)
+        shape.workspace = _ptr(ws)
+        nbytes = int(lib.lsn_dcn_backward_workspace_bytes(ctypes.byref(shape), 1, levels))
+        gws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes > 0 else None
+        if gws is not None:
+            shape.gather_workspace, shape.gather_workspace_bytes = gws.data_ptr(), nbytes
+        return shape, levels, gws
+
+    shape, levels, gws = backward_args(gd)
+    q = lib.lsn_dcn_prepared_ok(ctypes.byref(shape), 1, levels, 1)
+    shape.weights_prepared = 1
+    if q:
+        img = weight_image(wd, 2, 1, cfg['pad'], cfg['dil'])
+        shape.workspace = _ptr(img)
+    rc = lib.lsn_dcn_backward(ctypes.byref(shape), 1, levels, _ptr(wd), _ptr(gw), _ptr(gb), 1, _stream()) if call else 0
+    verdict('prepared_bwd', q, rc, 'lsn_dcn_prepared_ok')
+    gwide = torch.randn((B, 2 * Co, Ho, Wo), device=dev).contiguous(memory_format=cl)   # grad_output: its first Co channels
+    shape, levels, gws = backward_args(gwide)
+    shape.out_pitch = 2 * Co
+    q = lib.lsn_dcn_pitched_ok(ctypes.byref(shape), 1, levels, 1)
+    rc = lib.lsn_dcn_backward(ctypes.byref(shape), 1, levels, _ptr(wd), _ptr(gw), _ptr(gb), 1, _stream()) if call else 0
+    verdict('pitched_bwd', q, rc)
+    torch.cuda.synchronize()
+    return answers
+
+
+@contextlib.contextmanager
+def _kernel_choice(choice):
+    mode, flag = KERNEL_CHOICES[choice]
+    old = _lib.get_math_mode()
+    _lib.set_debug_word(flag)
+    _lib.set_math_mode(mode)
+    try:
+        yield
+    finally:
+        _lib.set_math_mode(old)
+        _lib.set_debug_word(0)
+
+
+@pytest.mark.parametrize('choice', QUERY_CHOICES)
+@pytest.mark.parametrize('case', DCN_CASES, ids=[c['name'] for c in DCN_CASES])
+def test_dcn_queries_match_the_calls(case, choice):
+    """lsn_dcn_prepared_ok / lsn_dcn_pitched_ok and the calls they answer for read one route (csrc/dcn.hip route_forward /
+    route_backward): a call is refused exactly where its query said 0.  The refusals are argument checks in front of every
+    launch."""
+    with _kernel_choice(choice):
+        _dcn_query_answers(case)
+
+
+def test_dcn_queries_answer_both_ways():
+    """Under the defaults both answers occur among DCN_CASES for each of the four queries (so the test above cannot pass
+    vacuously): the head shapes are served, odd channel counts and grouped calls are not."""
+    with _kernel_choice('default'):
+        got = {c['name']: _dcn_query_answers(c, call=False) for c in DCN_CASES}
+    for name in ('prepared_fwd', 'pitched_fwd', 'prepared_bwd', 'pitched_bwd'):
+        assert {a[name] for a in got.values()} == {0, 1}, (name, {k: a[name] for k, a in got.items()})
+        assert got['v2_head_p6'][name] == 1 and got['pyr_head'][name] == 1, (name, got['v2_head_p6'], got['pyr_head'])
+        assert got['v2_c6_odd'][name] == 0, (name, got['v2_c6_odd'])
+        assert all(a[name] == 0 for k, a in got.items() if next(c for c in DCN_CASES if c['name'] == k).get('groups', 1) > 1), name
 
 
 def test_dcn_multi_level_launch_equals_single():
@@ -686,7 +824,7 @@ CONV_CASES = [
     (1, 208, 27, 3, 2, 1, 1, 6, 8, True),         # ... at the Res2Net per-scale widths
     (1, 104, 27, 3, 2, 1, 1, 12, 16, True),
     (1, 52, 27, 3, 2, 1, 1, 24, 32, True),
-    # weight gradients on the deformable family's fragment-order kernel (csrc/dcn.hip conv_wgrad_dense_mm: 256 | Co, 64 | C and
+    # weight gradients on the deformable family's fragment-order kernel (csrc/dcn.hip conv_wgrad_dense_mm_ok: 256 | Co, 64 | C and
     # 3x3 at >= 4096 output pixels / wide 1x1 at >= 2048 / strided 1x1 from >= 512 channels) -- the rows above stay below
     # its thresholds, and a pitch the dense caller left unset went unnoticed in round 4 until the benchmark's loss moved
     (2, 64, 256, 3, 1, 1, 1, 48, 50, True),
