@@ -320,6 +320,51 @@ int lsn_offset_chain_backward(int n_levels, const lsn_offset_chain_level *levels
 int lsn_topk_columns(const float *x, int P, int G, int ldx, int nseg, const int *seg_start, const int *seg_len, int k,
                      int largest, float *values, int64_t *indices, lsn_stream_t stream);
 
+/* ---- target assignment: centroid_assigner.py:26-93, atss_assigner.py:29-164 ----------------------
+ * The step between "predictions" and "loss": which ground truth every grid point (init stage) / decoded box (refine stage)
+ * regresses to.  gt_inds (int64): 0 = background, k > 0 = 1-based row of the assigned gt; labels = gt_labels[k - 1] or -1
+ * (labels and gt_labels are both given or both NULL).  No (P x G) matrix is built: `workspace` holds
+ * lsn_assign_workspace_bytes(P, G, nlev, k) bytes, O(P + G * nlev * k), contents undefined (Centroid: nlev = 1, k = pos_num;
+ * ATSS: P = N, k = topk).  Three launches per call, asynchronous on `stream`, no allocation, no host read; the results do
+ * not depend on the order in which workgroups run.  P == 0 or G == 0 is LSN_ERR_INVALID: an empty assignment needs no
+ * library.  Arithmetic: csrc/assign_rows.h, separately rounded fp32 operations as the reference's tensor statements.
+ *
+ * Centroid: every gt takes the pos_num nearest points (|| (xy - centre) / wh ||_2, wh clamped at 1e-6) of ITS level --
+ * int((log2(w / scale) + log2(h / scale)) / 2) clamped to the levels int(log2(stride)) present among the points -- equal
+ * distances by ascending point row, fewer when the level has fewer points; a point that several gts took keeps the
+ * nearest, equal distances the lowest gt row.  centres: (G, 2) or NULL = the box centres.  NaN distances never take a
+ * point.
+ *
+ * ATSS: every gt takes, on each of the nlev <= 8 levels (level_len: host array, sum = N, each >= topk), the topk boxes
+ * whose centres are nearest to its centre (equal distances by ascending row); threshold = mean + unbiased standard
+ * deviation of the IoUs (overlap / max(area1 + area2 - overlap, 1e-6)) of these nlev * topk candidates; a candidate is
+ * positive when its IoU >= threshold and its centre lies more than 0.01 inside the gt; a box keeps the positive gt of
+ * highest IoU, equal IoUs the lowest gt row.  max_overlaps (N, may be NULL): that IoU, -1e8 for background.  bboxes: N rows
+ * of ld >= 4 floats, x1 y1 x2 y2 first.
+ *
+ * _batch: B <= 64 images in one call.  gt_offset (host, B + 1 ints, gt_offset[0] = 0): the gts of image b are rows
+ * [gt_offset[b], gt_offset[b + 1]) of gt_bboxes / centres / gt_labels, an image may have none; gt_inds counts within the
+ * image.  The points / level_len are shared; bboxes holds B * N rows, outputs are (B, P) / (B, N).  Workspace:
+ * lsn_assign_workspace_bytes(B * P, gt_offset[B], nlev, k).  [fused: replaces ~100 ATen launches per image and stage] */
+int64_t lsn_assign_workspace_bytes(int P, int G, int nlev, int k);
+int lsn_centroid_assign(const float *points /* (P,3): x, y, stride */, int P, const float *gt_bboxes /* (G,4) */,
+                        const float *centres /* (G,2) or NULL */, int G, float scale, int pos_num,
+                        const int64_t *gt_labels /* (G) or NULL */, int64_t *gt_inds /* (P) */,
+                        int64_t *labels /* (P) or NULL */, void *workspace, lsn_stream_t stream);
+int lsn_centroid_assign_batch(const float *points, int P, const float *gt_bboxes, const float *centres, int B,
+                              const int *gt_offset, float scale, int pos_num, const int64_t *gt_labels, int64_t *gt_inds,
+                              int64_t *labels, void *workspace, lsn_stream_t stream);
+int lsn_atss_assign(const float *bboxes, int ld /* >= 4 */, int N, int nlev, const int *level_len, const float *gt_bboxes,
+                    int G, int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps, int64_t *labels,
+                    void *workspace, lsn_stream_t stream);
+int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int B,
+                          const int *gt_offset, int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps,
+                          int64_t *labels, void *workspace, lsn_stream_t stream);
+/* out[p] = gt_inds[p] > 0 ? table[gt_inds[p] - 1] : 0 over rows of D floats: the per-point regression targets (boxes,
+ * extreme points, polygons, keypoints side by side in one (G, D) table) of an assignment, one launch. */
+int lsn_dense_targets(const int64_t *gt_inds, int P, const float *table /* (G, D) */, int D, float *out /* (P, D) */,
+                      lsn_stream_t stream);
+
 /* ---- NMS: nms_ext.cpp:18-29 ---------------------------------------------------------------- */
 /* dets (n,5) = x1,y1,x2,y2,score on the device.  keep (capacity n, int64, device) receives the
  * kept indices into the INPUT order, in descending score order; *num_keep (device int64) their

@@ -119,6 +119,8 @@ EXPORTS = [
     'lsn_image_prep_u8', 'lsn_cross_iou_bbox_forward', 'lsn_cross_iou_bbox_backward',
     'lsn_cross_iou_bbox_stage_forward', 'lsn_cross_iou_bbox_stage_backward',
     'lsn_cross_iou_rows_forward', 'lsn_cross_iou_rows_backward',
+    'lsn_assign_workspace_bytes', 'lsn_centroid_assign', 'lsn_centroid_assign_batch', 'lsn_atss_assign', 'lsn_atss_assign_batch',
+    'lsn_dense_targets',
 ]
 
 _lib = None
@@ -136,6 +138,7 @@ def load():
     lib = ctypes.CDLL(SO_PATH)
     lib.lsn_last_error.restype = ctypes.c_char_p
     lib.lsn_nms_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_assign_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_group_norm_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_bn_eval_act_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_dcn_backward_workspace_bytes.restype = ctypes.c_int64

@@ -6,7 +6,14 @@
 
 Same arithmetic and tie behaviour as the reference (bit-exact gt indices are part of the parity
 contract), written with `where`/`scatter` instead of masked assignment so that nothing depends on
-host-side shapes."""
+host-side shapes.
+
+On the device the two assigners run as kernels of the library (`lsn_centroid_assign`, `lsn_atss_assign`: csrc/assign.hip,
+arithmetic in csrc/assign_rows.h) -- same integers, no (points x gts) matrix.  The torch statements below stay as they
+are: the checker of those kernels and the path of host tensors, other dtypes, levels shorter than `topk` and
+LSNET_NATIVE_ASSIGN=0."""
+import os
+
 import torch
 
 from ..utils.registry import Registry, build_from_cfg
@@ -14,6 +21,20 @@ from ..utils.registry import Registry, build_from_cfg
 BBOX_ASSIGNERS = Registry('bbox_assigner')
 BBOX_SAMPLERS = Registry('bbox_sampler')
 IOU_CALCULATORS = Registry('IoU calculator')
+# LSNET_NATIVE_ASSIGN=0: the torch statements on the device too (A/B switch; the tests compare the two)
+NATIVE_ASSIGN = os.environ.get('LSNET_NATIVE_ASSIGN', '1') != '0'
+
+
+def _native(*tensors):
+    """The library's assignment kernels take these tensors (None: an optional one that is absent)."""
+    return NATIVE_ASSIGN and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+
+
+def _long_labels(gt_labels):
+    """per-image label list the kernels can gather from (int64 throughout), else None: labels then come from torch"""
+    if gt_labels is None or any(l is None or l.dtype != torch.long for l in gt_labels):
+        return None
+    return gt_labels
 
 
 def build_assigner(cfg, **default_args):
@@ -119,6 +140,8 @@ class CentroidAssigner:
         num_gts, num_points = gt_bboxes.shape[0], points.shape[0]
         if num_gts == 0 or num_points == 0:
             return _empty_assignment(points, num_gts, num_points, gt_labels, False)
+        if _native(points, gt_bboxes, gt_extreme_pts if self.iou_type == 'centroid' else None):
+            return self.assign_batch(points, [gt_bboxes], [gt_extreme_pts], None if gt_labels is None else [gt_labels])[0]
         xy = points[:, :2]
         lvl = torch.log2(points[:, 2]).int()
         lvl_min, lvl_max = lvl.min(), lvl.max()
@@ -136,6 +159,27 @@ class CentroidAssigner:
         best_d, best_gt = claimed.min(dim=1)
         gt_inds = torch.where(best_d != INF, best_gt + 1, 0)
         return AssignResult(num_gts, gt_inds, None, labels=_labels_of(gt_inds, gt_labels))
+
+    def assign_batch(self, points, gt_bboxes, gt_extreme_pts, gt_labels=None):
+        """All images of a batch over the SAME points in one call of the library: gt_bboxes / gt_extreme_pts / gt_labels are
+        per-image lists (an image may have no gt).  -> list of AssignResult, or None when the kernels do not take the
+        inputs (the caller then assigns image by image)."""
+        centroid = self.iou_type == 'centroid'
+        if points.shape[0] == 0 or sum(g.shape[0] for g in gt_bboxes) == 0 or not _native(points, *gt_bboxes) or \
+                (centroid and not _native(*gt_extreme_pts)):
+            return None
+        from ..ops.backend import get_backend
+        centres = None
+        if centroid:
+            centres = [self.gen_centroid(e, g.shape[0]) if g.shape[0] else g.new_zeros((0, 2))
+                       for g, e in zip(gt_bboxes, gt_extreme_pts)]
+        lab = _long_labels(gt_labels)
+        gt_inds, labels = get_backend(points).centroid_assign_batch(points[:, :3], [g[:, :4] for g in gt_bboxes], centres,
+                                                                    float(self.scale), self.pos_num, lab)
+        return [AssignResult(g.shape[0], gt_inds[i], None,
+                             labels=labels[i] if lab is not None else
+                             _labels_of(gt_inds[i], None if gt_labels is None else gt_labels[i]))
+                for i, g in enumerate(gt_bboxes)]
 
     @staticmethod
     def gen_centroid(pts, num_gts):
@@ -254,12 +298,40 @@ class ATSSAssigner:
         self.topk = topk
         self.iou_calculator = build_iou_calculator(iou_calculator)
 
+    def _native_levels(self, num_level_bboxes, num_bboxes):
+        """The kernel takes up to 8 levels of at least `topk` boxes (torch's topk raises on a shorter one: that error stays
+        the torch path's) and computes the IoU of BboxOverlaps2D."""
+        return type(self.iou_calculator) is BboxOverlaps2D and 1 <= len(num_level_bboxes) <= 8 and \
+            all(n >= self.topk for n in num_level_bboxes) and sum(num_level_bboxes) == num_bboxes
+
+    def assign_batch(self, bboxes, num_level_bboxes, gt_bboxes, gt_labels=None):
+        """bboxes (B, N, >= 4): the boxes of all images, the same levels in each; gt_bboxes / gt_labels: per-image lists (an
+        image may have no gt).  -> list of AssignResult, or None when the kernels do not take the inputs."""
+        if bboxes.shape[1] == 0 or sum(g.shape[0] for g in gt_bboxes) == 0 or not _native(bboxes, *gt_bboxes) or \
+                not self._native_levels(num_level_bboxes, bboxes.shape[1]):
+            return None
+        from ..ops.backend import get_backend
+        lab = _long_labels(gt_labels)
+        gt_inds, max_overlaps, labels = get_backend(bboxes).atss_assign_batch(bboxes[..., :4], num_level_bboxes,
+                                                                              [g[:, :4] for g in gt_bboxes], self.topk, lab)
+        out = []
+        for i, g in enumerate(gt_bboxes):
+            if g.shape[0] == 0:     # (as `assign` answers an image without gts: overlaps 0, not -INF)
+                out.append(_empty_assignment(bboxes[i], 0, bboxes.shape[1], None if gt_labels is None else gt_labels[i], True))
+                continue
+            out.append(AssignResult(g.shape[0], gt_inds[i], max_overlaps[i],
+                                    labels=labels[i] if lab is not None else
+                                    _labels_of(gt_inds[i], None if gt_labels is None else gt_labels[i])))
+        return out
+
     def assign(self, bboxes, num_level_bboxes, gt_bboxes, gt_bboxes_ignore=None, gt_labels=None):
         INF = 100000000
         bboxes = bboxes[:, :4]
         num_gt, num_bboxes = gt_bboxes.size(0), bboxes.size(0)
         if num_gt == 0 or num_bboxes == 0:
             return _empty_assignment(bboxes, num_gt, num_bboxes, gt_labels, True)
+        if _native(bboxes, gt_bboxes) and self._native_levels(num_level_bboxes, num_bboxes):
+            return self.assign_batch(bboxes[None], num_level_bboxes, [gt_bboxes], None if gt_labels is None else [gt_labels])[0]
         overlaps = self.iou_calculator(bboxes, gt_bboxes)                      # (N, G)
         gt_c = torch.stack(((gt_bboxes[:, 0] + gt_bboxes[:, 2]) / 2.0, (gt_bboxes[:, 1] + gt_bboxes[:, 3]) / 2.0), 1)
         cx, cy = (bboxes[:, 0] + bboxes[:, 2]) / 2.0, (bboxes[:, 1] + bboxes[:, 3]) / 2.0

@@ -1,0 +1,353 @@
+// Target assignment of liblsnet_hip.so: CentroidAssigner, ATSSAssigner and the dense-target gather of LSHead.loss().
+#include "common.h"
+#include "assign_rows.h"
+
+namespace lsn {
+
+// ---------------------------------------------------------------------------------------------
+// Both assigners (lsnet_amd/core/assigners.py; centroid_assigner.py:26-93, atss_assigner.py:29-164) are "every gt picks its
+// k nearest rows of a row segment, then every row keeps the best gt that picked it".  The torch statement goes through a
+// (P, G) distance matrix, a (P, G) IoU matrix and a (G, P) table; here nothing of that size exists:
+//   1. one workgroup per (gt, segment) computes the segment's distances on the fly from 3 / 4 floats per row, keeps them
+//      in LDS as order-preserving keys and runs k rounds of a workgroup-wide minimum over (key, row) -- the selection of
+//      topk_cols_kernel (misc.hip) with its tie rule, equal distances by ascending row;
+//   2. the picks meet in one 64-bit word per row, (value key << 32 | gt) under a vector atomicMin (Centroid: smallest
+//      distance, equal distances to the lowest gt) or (IoU key << 32 | ~gt) under atomicMax (ATSS: highest IoU, equal
+//      IoUs to the lowest gt).  Integer min / max commute: the word does not depend on the order of arrival;
+//   3. a per-row kernel turns the words into gt_inds / labels / max_overlaps.
+// Three launches per call, for one image or a batch.  Workspace: the words, the points' levels and the ATSS candidate
+// lists -- O(P + G * nlev * k).
+// ---------------------------------------------------------------------------------------------
+constexpr int ASSIGN_MAX_IMAGES = 64;
+constexpr unsigned ASSIGN_SKIP = 0xffffffffu;      // key of a row that is no candidate (other level, NaN distance)
+
+struct AssignBatch {
+    int B;
+    int off[ASSIGN_MAX_IMAGES + 1];   // gt rows of image b: [off[b], off[b + 1])
+};
+
+__device__ __forceinline__ int assign_image_of(const AssignBatch &bt, int g)
+{
+    int b = 0;
+    while (b + 1 < bt.B && g >= bt.off[b + 1]) ++b;
+    return b;
+}
+
+// The k smallest (key, row) pairs of rows [0, n), ascending, rows whose key is ASSIGN_SKIP left out; emit(r, row, key) runs
+// on thread 0 for every pick.  keys: LDS for the first nc rows, the others are recomputed in every round.  All 1024 threads
+// of the workgroup call it.
+template <class KeyFn, class Emit>
+__device__ __forceinline__ void assign_select(int n, int nc, unsigned *keys, unsigned long long *red, int k, KeyFn keyfn, Emit emit)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < nc; i += 1024) keys[i] = keyfn(i);
+    __syncthreads();
+    unsigned long long last = 0;
+    bool first = true;
+    for (int r = 0; r < k; ++r) {
+        unsigned long long best = ~0ull;
+        for (int i = tid; i < n; i += 1024) {
+            const unsigned key = i < nc ? keys[i] : keyfn(i);
+            const unsigned long long c = ((unsigned long long)key << 32) | (unsigned)i;
+            if (key != ASSIGN_SKIP && (first || c > last) && c < best) best = c;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(best, o);
+            best = t < best ? t : best;
+        }
+        if ((tid & 63) == 0) red[tid >> 6] = best;
+        __syncthreads();
+        best = red[0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) best = red[w] < best ? red[w] : best;
+        __syncthreads();
+        if (best == ~0ull) break;             // fewer than k candidates (the same value in every thread)
+        if (tid == 0) emit(r, (int)(best & 0xffffffffu), (unsigned)(best >> 32));
+        last = best, first = false;
+    }
+}
+
+// ---- Centroid ----------------------------------------------------------------------------------
+// workspace: int hdr[4] = {lvl_min, lvl_max} | int lvl[P] | (8-byte aligned) u64 word[B * P]
+__host__ __device__ inline size_t centroid_words_offset(int P) { return (16 + (size_t)P * 4 + 7) / 8 * 8; }
+
+// workgroup 0: the points' levels and their range; every workgroup b: the words of image b
+__global__ __launch_bounds__(1024) void centroid_prep_kernel(const float *__restrict__ points, int P, int *__restrict__ hdr,
+                                                             int *__restrict__ lvl, unsigned long long *__restrict__ word)
+{
+    __shared__ int red[32];
+    const int tid = threadIdx.x;
+    unsigned long long *w = word + (size_t)blockIdx.x * P;
+    for (int i = tid; i < P; i += 1024) w[i] = ~0ull;
+    if (blockIdx.x != 0) return;
+    int lo = 0x7fffffff, hi = -0x7fffffff;
+    for (int i = tid; i < P; i += 1024) {
+        const int l = assign_point_level(points[(size_t)i * 3 + 2]);
+        lvl[i] = l;
+        lo = l < lo ? l : lo, hi = l > hi ? l : hi;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
+        lo = a < lo ? a : lo, hi = b > hi ? b : hi;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = lo, red[16 + (tid >> 6)] = hi;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w2 = 1; w2 < 16; ++w2) lo = red[w2] < lo ? red[w2] : lo, hi = red[16 + w2] > hi ? red[16 + w2] : hi;
+        hdr[0] = lo, hdr[1] = hi;
+    }
+}
+
+// one workgroup per gt: its pos_num nearest points of its level claim their words
+__global__ __launch_bounds__(1024) void centroid_claim_kernel(const float *__restrict__ points, int P, const float *__restrict__ gt,
+                                                              const float *__restrict__ centres, AssignBatch bt, float scale,
+                                                              int pos_num, const int *__restrict__ hdr, const int *__restrict__ lvl,
+                                                              unsigned long long *__restrict__ word, int cap)
+{
+    extern __shared__ unsigned keys[];
+    __shared__ unsigned long long red[16];
+    const int g = blockIdx.x, b = assign_image_of(bt, g);
+    const float *box = gt + (size_t)g * 4;
+    const float w = assign_gt_extent(box[0], box[2]), h = assign_gt_extent(box[1], box[3]);
+    const float cx = centres ? centres[(size_t)g * 2] : assign_box_centre(box[0], box[2]);
+    const float cy = centres ? centres[(size_t)g * 2 + 1] : assign_box_centre(box[1], box[3]);
+    const int gl = assign_gt_level(w, h, scale, hdr[0], hdr[1]);
+    unsigned long long *wd = word + (size_t)b * P;
+    const unsigned gi = (unsigned)(g - bt.off[b]);
+    assign_select(
+        P, P < cap ? P : cap, keys, red, pos_num,
+        [&](int i) {
+            if (lvl[i] != gl) return ASSIGN_SKIP;
+            return assign_key(assign_centroid_distance(points[(size_t)i * 3], points[(size_t)i * 3 + 1], cx, cy, w, h));
+        },
+        [&](int, int row, unsigned key) { atomicMin(wd + row, ((unsigned long long)key << 32) | gi); });
+}
+
+// ---- ATSS --------------------------------------------------------------------------------------
+struct AtssLevels {
+    int n, start[8], len[8];
+};
+
+// workspace: u64 word[B * N] | int cand_row[G * nlev * k] | float cand_iou[G * nlev * k]
+// one workgroup per (gt, level): the level's topk boxes with the nearest centres -> the gt's candidate list; all workgroups
+// together clear the words
+__global__ __launch_bounds__(1024) void atss_candidates_kernel(const float *__restrict__ boxes, int ld, int N, AtssLevels lv,
+                                                               const float *__restrict__ gt, AssignBatch bt, int topk,
+                                                               unsigned long long *__restrict__ word, int *__restrict__ cand_row,
+                                                               float *__restrict__ cand_iou, int cap)
+{
+    extern __shared__ unsigned keys[];
+    __shared__ unsigned long long red[16];
+    const int g = blockIdx.x, sg = blockIdx.y, b = assign_image_of(bt, g), tid = threadIdx.x;
+    const size_t nword = (size_t)bt.B * N, nthr = (size_t)gridDim.x * gridDim.y * 1024;
+    for (size_t i = ((size_t)sg * gridDim.x + g) * 1024 + tid; i < nword; i += nthr) word[i] = 0ull;
+    const float *box = gt + (size_t)g * 4;
+    const float gx = assign_box_centre(box[0], box[2]), gy = assign_box_centre(box[1], box[3]);
+    const int start = lv.start[sg], n = lv.len[sg];
+    const float *seg = boxes + ((size_t)b * N + start) * ld;
+    const size_t slot = ((size_t)g * lv.n + sg) * topk;
+    for (int r = tid; r < topk; r += 1024) cand_row[slot + r] = -1;      // (a level with NaN distances fills fewer)
+    assign_select(
+        n, n < cap ? n : cap, keys, red, topk,
+        [&](int i) {
+            const float *q = seg + (size_t)i * ld;
+            return assign_key(assign_centre_distance(assign_box_centre(q[0], q[2]), assign_box_centre(q[1], q[3]), gx, gy));
+        },
+        [&](int r, int row, unsigned) {
+            cand_row[slot + r] = start + row;
+            cand_iou[slot + r] = assign_iou(seg + (size_t)row * ld, box);
+        });
+}
+
+// one thread per gt: threshold over its candidates, the positives raise their words
+__global__ __launch_bounds__(64) void atss_positive_kernel(const float *__restrict__ boxes, int ld, int N, int ncand,
+                                                           const float *__restrict__ gt, AssignBatch bt, int G,
+                                                           unsigned long long *__restrict__ word, const int *__restrict__ cand_row,
+                                                           float *__restrict__ cand_iou)
+{
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= G) return;
+    const int b = assign_image_of(bt, g);
+    const int *rows = cand_row + (size_t)g * ncand;
+    float *iou = cand_iou + (size_t)g * ncand;
+    int n = 0;
+    for (int i = 0; i < ncand; ++i)           // close the gaps a short candidate list leaves (NaN distances only)
+        if (rows[i] >= 0) iou[n++] = iou[i];
+    const float thr = assign_atss_threshold(iou, n);
+    const float *box = gt + (size_t)g * 4;
+    const unsigned gi = ~(unsigned)(g - bt.off[b]);
+    for (int i = 0, j = 0; i < ncand; ++i) {
+        if (rows[i] < 0) continue;
+        const float v = iou[j++];
+        const float *q = boxes + ((size_t)b * N + rows[i]) * ld;
+        if (v >= thr && assign_centre_inside(assign_box_centre(q[0], q[2]), assign_box_centre(q[1], q[3]), box))
+            atomicMax(word + (size_t)b * N + rows[i], ((unsigned long long)assign_key(v) << 32) | gi);
+    }
+}
+
+// ---- the words -> gt_inds, labels, max_overlaps ---------------------------------------------------
+template <bool ATSS>
+__global__ __launch_bounds__(256) void assign_resolve_kernel(const unsigned long long *__restrict__ word, int P, AssignBatch bt,
+                                                             const int64_t *__restrict__ gt_labels, int64_t *__restrict__ gt_inds,
+                                                             int64_t *__restrict__ labels, float *__restrict__ max_overlaps)
+{
+    const size_t total = (size_t)bt.B * P;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const unsigned long long w = word[i];
+        const bool hit = ATSS ? w != 0ull : w != ~0ull;
+        const unsigned lo = (unsigned)(w & 0xffffffffu);
+        const int gi = (int)(ATSS ? ~lo : lo);
+        gt_inds[i] = hit ? gi + 1 : 0;
+        if (labels) labels[i] = hit ? gt_labels[bt.off[(int)(i / P)] + gi] : -1;
+        if (ATSS && max_overlaps) max_overlaps[i] = hit ? assign_key_value((unsigned)(w >> 32)) : -1e8f;
+    }
+}
+
+// ---- dense targets -----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dense_targets_kernel(const int64_t *__restrict__ gt_inds, size_t total, int D,
+                                                            const float *__restrict__ table, float *__restrict__ out)
+{
+    for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t p = e / D;
+        const int64_t g = gt_inds[p];
+        out[e] = g > 0 ? table[(size_t)(g - 1) * D + (e - p * D)] : 0.f;
+    }
+}
+
+// LDS keys a selection workgroup may hold on the current device (as lsn_topk_columns sizes them); < 0: error raised
+static int select_lds_cap(const void *kernel, int nmax)
+{
+    int dev = 0, lds_max = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(LSN_ERR_RUNTIME, "assign: hipGetDevice failed");
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || lds_max <= 0)
+        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess)
+            return fail(LSN_ERR_RUNTIME, "assign: hipDeviceGetAttribute failed");
+    int cap_max = (lds_max - 4096) / 4;
+    if (cap_max > 36 * 1024) cap_max = 36 * 1024;
+    if (cap_max < 1024) return fail(LSN_ERR_UNSUPPORTED, "assign: device offers %d bytes of LDS per workgroup", lds_max);
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cap_max * 4) != hipSuccess)
+        return fail(LSN_ERR_RUNTIME, "assign: hipFuncSetAttribute failed");
+    return nmax < cap_max ? nmax : cap_max;
+}
+
+static int make_batch(AssignBatch &bt, int B, const int *gt_offset, const char *what)
+{
+    LSN_CHECK(B >= 1 && B <= ASSIGN_MAX_IMAGES, "%s: %d images (1 .. %d)", what, B, ASSIGN_MAX_IMAGES);
+    LSN_CHECK(gt_offset && gt_offset[0] == 0, "%s: gt_offset must start at 0", what);
+    bt.B = B;
+    for (int b = 0; b <= B; ++b) {
+        LSN_CHECK(b == 0 || gt_offset[b] >= gt_offset[b - 1], "%s: gt_offset must not decrease", what);
+        bt.off[b] = gt_offset[b];
+    }
+    return 0;
+}
+
+static inline int resolve_blocks(size_t total) { return (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024); }
+
+}  // namespace lsn
+
+using namespace lsn;
+
+int64_t lsn_assign_workspace_bytes(int P, int G, int nlev, int k)
+{
+    if (P < 0 || G < 0 || nlev < 0 || k < 0) return 0;
+    const int64_t cand = (int64_t)G * (nlev > 1 ? nlev : 1) * (k > 1 ? k : 1);
+    return 64 + (int64_t)P * 12 + cand * 8;       // header + levels + words, candidate rows + IoUs
+}
+
+int lsn_centroid_assign_batch(const float *points, int P, const float *gt_bboxes, const float *centres, int B,
+                              const int *gt_offset, float scale, int pos_num, const int64_t *gt_labels, int64_t *gt_inds,
+                              int64_t *labels, void *workspace, lsn_stream_t stream)
+{
+    AssignBatch bt;
+    if (int rc = make_batch(bt, B, gt_offset, "centroid assign")) return rc;
+    const int G = bt.off[B];
+    LSN_CHECK(P > 0 && G > 0, "centroid assign: P = %d, G = %d (empty inputs are the caller's)", P, G);
+    LSN_CHECK(pos_num > 0 && scale > 0.f, "centroid assign: pos_num %d, scale %g", pos_num, (double)scale);
+    LSN_CHECK(points && gt_bboxes && gt_inds && workspace, "centroid assign: NULL argument");
+    LSN_CHECK((labels == nullptr) == (gt_labels == nullptr), "centroid assign: labels and gt_labels go together");
+    LSN_CHECK((long long)B * P < (1ll << 31), "centroid assign: %d x %d points", B, P);
+    char *ws = static_cast<char *>(workspace);
+    int *hdr = reinterpret_cast<int *>(ws), *lvl = hdr + 4;
+    unsigned long long *word = reinterpret_cast<unsigned long long *>(ws + centroid_words_offset(P));
+    const int cap = select_lds_cap(reinterpret_cast<const void *>(centroid_claim_kernel), P);
+    if (cap < 0) return cap;
+    hipLaunchKernelGGL(centroid_prep_kernel, dim3(B), dim3(1024), 0, stream, points, P, hdr, lvl, word);
+    hipLaunchKernelGGL(centroid_claim_kernel, dim3(G), dim3(1024), (size_t)cap * 4, stream, points, P, gt_bboxes, centres, bt,
+                       scale, pos_num, hdr, lvl, word, cap);
+    hipLaunchKernelGGL(assign_resolve_kernel<false>, dim3(resolve_blocks((size_t)B * P)), dim3(256), 0, stream, word, P, bt,
+                       gt_labels, gt_inds, labels, static_cast<float *>(nullptr));
+    LSN_HIP(hipGetLastError());
+    return 0;
+}
+
+int lsn_centroid_assign(const float *points, int P, const float *gt_bboxes, const float *centres, int G, float scale,
+                        int pos_num, const int64_t *gt_labels, int64_t *gt_inds, int64_t *labels, void *workspace,
+                        lsn_stream_t stream)
+{
+    const int off[2] = {0, G};
+    return lsn_centroid_assign_batch(points, P, gt_bboxes, centres, 1, off, scale, pos_num, gt_labels, gt_inds, labels,
+                                     workspace, stream);
+}
+
+int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int B,
+                          const int *gt_offset, int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps,
+                          int64_t *labels, void *workspace, lsn_stream_t stream)
+{
+    AssignBatch bt;
+    if (int rc = make_batch(bt, B, gt_offset, "atss assign")) return rc;
+    const int G = bt.off[B];
+    LSN_CHECK(N > 0 && G > 0, "atss assign: N = %d, G = %d (empty inputs are the caller's)", N, G);
+    LSN_CHECK(ld >= 4 && topk > 0, "atss assign: ld %d, topk %d", ld, topk);
+    LSN_CHECK(nlev >= 1 && nlev <= 8 && level_len, "atss assign: %d levels (1 .. 8)", nlev);
+    AtssLevels lv;
+    lv.n = nlev;
+    int start = 0, nmax = 0;
+    for (int i = 0; i < nlev; ++i) {
+        LSN_CHECK(level_len[i] >= topk, "atss assign: level %d has %d boxes, topk = %d", i, level_len[i], topk);
+        lv.start[i] = start, lv.len[i] = level_len[i];
+        start += level_len[i];
+        nmax = level_len[i] > nmax ? level_len[i] : nmax;
+    }
+    LSN_CHECK(start == N, "atss assign: the levels hold %d boxes, N = %d", start, N);
+    LSN_CHECK(bboxes && gt_bboxes && gt_inds && workspace, "atss assign: NULL argument");
+    LSN_CHECK((labels == nullptr) == (gt_labels == nullptr), "atss assign: labels and gt_labels go together");
+    LSN_CHECK((long long)B * N < (1ll << 31), "atss assign: %d x %d boxes", B, N);
+    char *ws = static_cast<char *>(workspace);
+    unsigned long long *word = reinterpret_cast<unsigned long long *>(ws);
+    const size_t ncand = (size_t)G * nlev * topk;
+    int *cand_row = reinterpret_cast<int *>(ws + (size_t)B * N * 8);
+    float *cand_iou = reinterpret_cast<float *>(cand_row + ncand);
+    const int cap = select_lds_cap(reinterpret_cast<const void *>(atss_candidates_kernel), nmax);
+    if (cap < 0) return cap;
+    hipLaunchKernelGGL(atss_candidates_kernel, dim3(G, nlev), dim3(1024), (size_t)cap * 4, stream, bboxes, ld, N, lv, gt_bboxes,
+                       bt, topk, word, cand_row, cand_iou, cap);
+    hipLaunchKernelGGL(atss_positive_kernel, dim3(cdiv(G, 64)), dim3(64), 0, stream, bboxes, ld, N, nlev * topk, gt_bboxes, bt, G,
+                       word, cand_row, cand_iou);
+    hipLaunchKernelGGL(assign_resolve_kernel<true>, dim3(resolve_blocks((size_t)B * N)), dim3(256), 0, stream, word, N, bt,
+                       gt_labels, gt_inds, labels, max_overlaps);
+    LSN_HIP(hipGetLastError());
+    return 0;
+}
+
+int lsn_atss_assign(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int G,
+                    int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps, int64_t *labels,
+                    void *workspace, lsn_stream_t stream)
+{
+    const int off[2] = {0, G};
+    return lsn_atss_assign_batch(bboxes, ld, N, nlev, level_len, gt_bboxes, 1, off, topk, gt_labels, gt_inds, max_overlaps,
+                                 labels, workspace, stream);
+}
+
+int lsn_dense_targets(const int64_t *gt_inds, int P, const float *table, int D, float *out, lsn_stream_t stream)
+{
+    LSN_CHECK(P >= 0 && D > 0, "dense targets: P = %d, D = %d", P, D);
+    if (P == 0) return 0;
+    LSN_CHECK(gt_inds && table && out, "dense targets: NULL argument");
+    const size_t total = (size_t)P * D;
+    hipLaunchKernelGGL(dense_targets_kernel, dim3(resolve_blocks(total) * 2), dim3(256), 0, stream, gt_inds, total, D, table, out);
+    LSN_HIP(hipGetLastError());
+    return 0;
+}

@@ -27,7 +27,8 @@ import torch.nn as nn
 from ...cnn import ConvModule, bias_init_with_prob, kaiming_init, normal_init
 from ...ops.conv import Conv2d
 from ...ops.group_norm import GroupNorm
-from ...core import PointGenerator, build_assigner, build_sampler, multiclass_nms_lsvr
+from ...core import PointGenerator, assigners, build_assigner, build_sampler, multiclass_nms_lsvr
+from ...ops.backend import get_backend
 from ...ops import ModulatedDeformConvPack, PyramidDeformConv
 from ...ops.dcn import offset_scale_chain
 from ...ops import cross_iou as fused_ciou
@@ -483,17 +484,27 @@ class LSHead(nn.Module):
         pos = gt_inds > 0
         idx = (gt_inds - 1).clamp(min=0)
         posf = pos.unsqueeze(1)
-        out = dict(bboxes_gt=torch.where(posf, gt_bboxes[idx], 0.0),          # python scalars: no tensor is made for them
+        fields = [('bboxes_gt', gt_bboxes)] + list(extra.items())
+        if assigners.NATIVE_ASSIGN and gt_inds.is_cuda and gt_inds.dtype == torch.long and \
+                all(v.is_cuda and v.dtype == torch.float32 and v.dim() == 2 for _, v in fields):
+            # one gather launch over the fields side by side (lsn_dense_targets) instead of an index + where pair per field
+            table = gt_bboxes if len(fields) == 1 else torch.cat([v for _, v in fields], dim=1)
+            rows = get_backend(table).dense_targets(gt_inds, table)
+            gathered = dict(zip([k for k, _ in fields], torch.split(rows, [v.shape[1] for _, v in fields], dim=1)))
+        else:
+            gathered = {k: torch.where(posf, v[idx], 0.0) for k, v in fields}   # python scalars: no tensor is made for them
+        out = dict(bboxes_gt=gathered['bboxes_gt'],
                    bbox_weights=posf.to(gt_bboxes.dtype).expand(-1, 4),
                    labels=torch.where(pos, gt_labels[idx] if gt_labels is not None else torch.ones_like(idx),
                                       self.background_label),
                    label_weights=torch.ones_like(pos, dtype=gt_bboxes.dtype), num_pos=pos.sum())
-        for k, v in extra.items():
-            out[k] = torch.where(posf, v[idx], 0.0)
+        for k in extra:
+            out[k] = gathered[k]
         return out
 
-    def _assign_image(self, stage, proposals, flags, all_valid, num_level, gt_bboxes, gt_labels, extra):
-        """One image, one stage -> dense target dict over ALL points (lsnet_head.py:796-917)."""
+    def _assign_image(self, stage, proposals, flags, all_valid, num_level, gt_bboxes, gt_labels, extra, res=None):
+        """One image, one stage -> dense target dict over ALL points (lsnet_head.py:796-917).  `res`: the image's
+        AssignResult when `_assign_batch` has computed it already."""
         n_all = proposals.shape[0]
         if gt_bboxes.shape[0] == 0:   # nothing to assign: all background
             zeros = proposals.new_zeros
@@ -505,7 +516,9 @@ class LSHead(nn.Module):
             return out
         inside = None if all_valid else flags
         props = proposals if inside is None else proposals[inside]
-        if stage == 'init':
+        if res is not None:
+            assert inside is None
+        elif stage == 'init':
             res = self.init_assigner.assign(props, gt_bboxes, extra.get('extremes_gt'), None, gt_labels)
         else:
             if inside is not None:
@@ -524,13 +537,33 @@ class LSHead(nn.Module):
             out = full
         return out
 
+    def _assign_batch(self, stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list):
+        """The stage's assignment of ALL images in one call of the library (every grid cell valid, so the images share points
+        and levels) -> per-image AssignResults, or None: the assigner has no batched form or its kernels do not take these
+        inputs, and the images are assigned one by one."""
+        assigner = self.init_assigner if stage == 'init' else self.refine_assigner
+        fn = getattr(assigner, 'assign_batch', None)
+        if fn is None:
+            return None
+        if stage == 'init':
+            points = proposals_list[0]
+            if any(p is not points for p in proposals_list):
+                return None
+            return fn(points, list(gt_bboxes_list), [e.get('extremes_gt') for e in extra_list])
+        if stacked is None:
+            return None
+        return fn(stacked, num_level, list(gt_bboxes_list))
+
     def get_targets(self, proposals_list, flags_list, all_valid, num_level, gt_bboxes_list, gt_labels_list,
-                    extra_list, stage):
+                    extra_list, stage, stacked=None):
         """All images of the batch -> per-level target tensors (B, N_l, ...) plus the positive count
-        sum_img max(n_pos, 1) as a DEVICE scalar (lsnet_head.py:919-1019)."""
+        sum_img max(n_pos, 1) as a DEVICE scalar (lsnet_head.py:919-1019).  `stacked`: the (B, N, 4) tensor whose rows
+        `proposals_list` holds, when there is one."""
+        results = self._assign_batch(stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list) if all_valid else None
         per_img = [self._assign_image(stage, proposals_list[i], flags_list[i], all_valid, num_level,
                                       gt_bboxes_list[i], None if gt_labels_list is None else gt_labels_list[i],
-                                      extra_list[i]) for i in range(len(proposals_list))]
+                                      extra_list[i], None if results is None else results[i])
+                   for i in range(len(proposals_list))]
         num_total_pos = sum(t['num_pos'].clamp(min=1) for t in per_img)
         out = {}
         for k in per_img[0]:
@@ -703,7 +736,7 @@ class LSHead(nn.Module):
         boxes = torch.cat(decoded, dim=1)
         return self.get_targets([boxes[i] for i in range(num_imgs)], init_stage['flat_flags'], init_stage['all_valid'],
                                 init_stage['num_level'], init_stage['gt_bboxes'], init_stage['gt_labels'], init_stage['extra'],
-                                'refine')
+                                'refine', stacked=boxes)
 
     def loss(self, cls_scores, bbox_pts_preds_init, bbox_pts_preds_refine, segm_pts_preds_init,
              segm_pts_preds_refine, pose_pts_preds_init, pose_pts_preds_refine, gt_bboxes, gt_extremes,

@@ -477,6 +477,97 @@ class HipBackend:
                                         _ptr(vals), _ptr(idx), _stream()))
         return vals, idx
 
+    # ------------------------------------------------------------------ target assignment
+    @staticmethod
+    def _assign_gts(gt_list, what):
+        """list of per-image (G_b, d) tensors -> (rows of all images, host offsets (B + 1), sum G)"""
+        offs = [0]
+        for t in gt_list:
+            offs.append(offs[-1] + t.shape[0])
+        rows = gt_list[0] if len(gt_list) == 1 else torch.cat(list(gt_list), 0)
+        if what is not None:
+            rows = _f32(rows, what)
+        return rows.contiguous(), (ctypes.c_int * len(offs))(*offs), offs[-1]
+
+    def centroid_assign_batch(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, out=None):
+        """points (P, 3) shared by the B images; gt_bboxes / centres / gt_labels: lists of B per-image tensors ((G_b, 4),
+        (G_b, 2) or None for the box centres, (G_b,) int64 or None).  -> (gt_inds (B, P) int64, labels (B, P) or None).
+        `out`: preallocated (gt_inds, labels, workspace) for callers that must not allocate (graph capture)."""
+        lib = _lib.load()
+        points = _f32(points, 'points').contiguous()
+        P, B = points.shape[0], len(gt_bboxes)
+        gts, offs, G = self._assign_gts(gt_bboxes, 'gt_bboxes')
+        cen = None if centres is None else self._assign_gts(centres, 'centres')[0]
+        lab = None if gt_labels is None else self._assign_gts(gt_labels, None)[0]
+        if lab is not None and lab.dtype != torch.int64:
+            raise TypeError(f'gt_labels must be int64, got {lab.dtype}')
+        nbytes = int(lib.lsn_assign_workspace_bytes(B * P, G, 1, int(pos_num)))
+        if out is None:
+            gt_inds = torch.empty((B, P), dtype=torch.int64, device=points.device)
+            labels = None if lab is None else torch.empty((B, P), dtype=torch.int64, device=points.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        else:
+            gt_inds, labels, ws = out
+            assert ws.numel() >= nbytes and gt_inds.numel() == B * P and gt_inds.is_contiguous()
+        _lib.check(lib.lsn_centroid_assign_batch(_ptr(points), P, _ptr(gts), _ptr(cen), B, offs, ctypes.c_float(scale),
+                                                 int(pos_num), _ptr(lab), _ptr(gt_inds), _ptr(labels), _ptr(ws), _stream()))
+        return gt_inds, labels
+
+    def centroid_assign(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, out=None):
+        """One image: -> (gt_inds (P,), labels (P,) or None); see centroid_assign_batch."""
+        gt_inds, labels = self.centroid_assign_batch(points, [gt_bboxes], None if centres is None else [centres], scale,
+                                                     pos_num, None if gt_labels is None else [gt_labels], out)
+        return gt_inds.view(-1), None if labels is None else labels.view(-1)
+
+    def atss_assign_batch(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, out=None):
+        """bboxes (B, N, >= 4) float32; level_len: the levels' box counts (sum = N, shared by the images); gt_bboxes /
+        gt_labels: lists of B per-image tensors.  -> (gt_inds (B, N), max_overlaps (B, N), labels (B, N) or None).
+        `out`: preallocated (gt_inds, max_overlaps, labels, workspace)."""
+        lib = _lib.load()
+        bboxes = _f32(bboxes, 'bboxes')
+        if bboxes.stride(2) != 1 or bboxes.stride(1) < bboxes.shape[2] or \
+                (bboxes.shape[0] > 1 and bboxes.stride(0) != bboxes.shape[1] * bboxes.stride(1)):
+            bboxes = bboxes.contiguous()
+        B, N = bboxes.shape[:2]
+        gts, offs, G = self._assign_gts(gt_bboxes, 'gt_bboxes')
+        assert len(offs) == B + 1
+        lab = None if gt_labels is None else self._assign_gts(gt_labels, None)[0]
+        if lab is not None and lab.dtype != torch.int64:
+            raise TypeError(f'gt_labels must be int64, got {lab.dtype}')
+        nlev = len(level_len)
+        lens = (ctypes.c_int * nlev)(*[int(v) for v in level_len])
+        nbytes = int(lib.lsn_assign_workspace_bytes(B * N, G, nlev, int(topk)))
+        if out is None:
+            gt_inds = torch.empty((B, N), dtype=torch.int64, device=bboxes.device)
+            overlaps = torch.empty((B, N), dtype=torch.float32, device=bboxes.device)
+            labels = None if lab is None else torch.empty((B, N), dtype=torch.int64, device=bboxes.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=bboxes.device)
+        else:
+            gt_inds, overlaps, labels, ws = out
+            assert ws.numel() >= nbytes and gt_inds.numel() == B * N and gt_inds.is_contiguous() and overlaps.is_contiguous()
+        _lib.check(lib.lsn_atss_assign_batch(_ptr(bboxes), bboxes.stride(1), N, nlev, lens, _ptr(gts), B, offs, int(topk),
+                                             _ptr(lab), _ptr(gt_inds), _ptr(overlaps), _ptr(labels), _ptr(ws), _stream()))
+        return gt_inds, overlaps, labels
+
+    def atss_assign(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, out=None):
+        """One image, bboxes (N, >= 4): -> (gt_inds (N,), max_overlaps (N,), labels (N,) or None)."""
+        gt_inds, overlaps, labels = self.atss_assign_batch(bboxes[None], level_len, [gt_bboxes], topk,
+                                                           None if gt_labels is None else [gt_labels], out)
+        return gt_inds.view(-1), overlaps.view(-1), None if labels is None else labels.view(-1)
+
+    def dense_targets(self, gt_inds, table):
+        """gt_inds (P,) int64 (0 = background, k = row k - 1), table (G, D) float32 -> (P, D): the assigned gt's row, zeros
+        for background -- torch.where(gt_inds[:, None] > 0, table[gt_inds - 1], 0) in one launch."""
+        lib = _lib.load()
+        table = _f32(table, 'table').contiguous()
+        gt_inds = gt_inds.contiguous()
+        if gt_inds.dtype != torch.int64:
+            raise TypeError(f'gt_inds must be int64, got {gt_inds.dtype}')
+        P, D = gt_inds.numel(), table.shape[1]
+        out = torch.empty((P, D), dtype=torch.float32, device=table.device)
+        _lib.check(lib.lsn_dense_targets(_ptr(gt_inds), P, _ptr(table), D, _ptr(out), _stream()))
+        return out
+
     # ------------------------------------------------------------------ LSHead's cumulative offset rescaling
     @staticmethod
     def offset_chain_ok(off):
