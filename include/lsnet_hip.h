@@ -720,6 +720,61 @@ int lsn_cross_iou_rows_backward(int kind, const float *pred, const float *target
                                 const float *bbox_gt, const float *vs, const float *weight, const float *grad_rows, int64_t n,
                                 int ncomp, int sub, float alpha, float eps, float *grad_pred, lsn_stream_t stream);
 
+/* ---- pooling and resampling (csrc/pool.hip; index, tie and divisor rules in csrc/pool_rows.h) ------------------------
+ * What the reference gets from the framework around its convolutions: the ResNet stem's MaxPool2d(3, 2, 1)
+ * (mmdet/models/backbones/resnet.py:567), the FPN's nearest upsample + add and its stride-2 extra levels
+ * (mmdet/models/necks/fpn.py:177-200), Res2Net's average pools (mmdet/models/backbones/res2net.py:80-99, 213-231) and the
+ * corner pools of the verification head (mmdet/ops/corner_pool/corner_pool.py:93-117).
+ * All tensors are float32 channels-last, (B, H, W, C) with C % 4 == 0.  Every tensor comes with its own PIXEL PITCH in
+ * floats (>= C, a multiple of 4; base pointers 16-byte aligned): a channel slice of a wider channels-last tensor is read,
+ * and a slot of a wider one is written, in place.  Image b of an (H, W) map starts at b * H * W * pitch.  Other shapes are
+ * refused with LSN_ERR_INVALID.  The calls allocate nothing, synchronise nothing, use no atomic operation -- every
+ * gradient element is summed by one lane in a fixed order, so the results are the same bits on every run -- and may be
+ * captured into a graph.  Outputs are overwritten unless `accumulate` says otherwise.
+ *
+ * lsn_pool_output_size: extent of the pooled map along one axis (the framework's rule; with ceil_mode a last window
+ * that would start in the right / bottom padding does not exist); 0 when there is no such pooling.
+ *
+ * Max pool.  y (B, Ho, Wo, C) = the window maximum; the first maximum in row-major window order wins, a NaN wins and
+ * propagates.  slot (B, Ho, Wo, C) bytes, dense, 4-byte aligned, may be NULL in the forward: the winning window position
+ * i * kw + j (kh * kw <= 255).  Backward: grad_x[p] = the sum, over the windows that cover p in ascending (oh, ow) order, of
+ * the grad_y whose slot names p; a 1 x 1 window needs no slot (NULL).  pad <= half the window. */
+int lsn_pool_output_size(int in, int k, int stride, int pad, int ceil_mode);
+int lsn_max_pool2d_forward(const float *x, int x_pitch, float *y, int y_pitch, uint8_t *slot, int B, int H, int W, int C, int kh,
+                           int kw, int stride, int pad, lsn_stream_t stream);
+int lsn_max_pool2d_backward(const float *grad_y, int gy_pitch, const uint8_t *slot, float *grad_x, int gx_pitch, int B, int H, int W,
+                            int C, int kh, int kw, int stride, int pad, lsn_stream_t stream);
+
+/* Average pool with the framework's output size and divisor rules: with ceil_mode the last window may hang over the border;
+ * it is clipped to the padded extent when count_include_pad is set and to the image otherwise.  The window is summed in
+ * row-major order and DIVIDED by the divisor.  Backward: grad_x[p] = the sum of grad_y / divisor over the windows that cover
+ * p, in ascending (oh, ow) order. */
+int lsn_avg_pool2d_forward(const float *x, int x_pitch, float *y, int y_pitch, int B, int H, int W, int C, int kh, int kw, int stride,
+                           int pad, int ceil_mode, int count_include_pad, lsn_stream_t stream);
+int lsn_avg_pool2d_backward(const float *grad_y, int gy_pitch, float *grad_x, int gx_pitch, int B, int H, int W, int C, int kh, int kw,
+                            int stride, int pad, int ceil_mode, int count_include_pad, lsn_stream_t stream);
+
+/* FPN top-down step: out[y, x] = lat[y, x] + top[y >> 1, x >> 1] for top (B, h, w, C) and lat, out (B, H, W, C) with, per
+ * axis, H == 2h or H == 2h - 1 -- the sizes for which index halving is nearest-neighbour interpolation; `out` may be `lat`.
+ * Backward: grad_top[y, x] = grad_out[2y, 2x] + [2y, 2x + 1] + [2y + 1, 2x] + [2y + 1, 2x + 1], in this order, the
+ * positions outside the map left out; accumulate != 0 adds the sum to what grad_top holds.  The gradient of `lat` is
+ * grad_out itself. */
+int lsn_upsample_add_forward(const float *top, int top_pitch, const float *lat, int lat_pitch, float *out, int out_pitch, int B, int h,
+                             int w, int H, int W, int C, lsn_stream_t stream);
+int lsn_upsample_add_backward(const float *grad_out, int go_pitch, float *grad_top, int gt_pitch, int accumulate, int B, int h, int w,
+                              int H, int W, int C, lsn_stream_t stream);
+
+/* Corner pool: the running maximum towards one border.  mode 0 = top (y[r] = max of the rows >= r), 1 = bottom, 2 = left
+ * (y[c] = max of the columns >= c), 3 = right.  accumulate != 0 adds the result to what y (forward) / grad_x (backward)
+ * holds: pool1(a) + pool2(b) is two launches.  Backward: the line is walked in scan order with the running maximum and its
+ * position; on a tie the LATEST position wins (the maximum nearest to the output position: torch.cummax's rule), a NaN
+ * wins; the gradients of the outputs that share a maximum are summed in scan order and stored at its position, every other
+ * position gets 0.  grad_x is a buffer of its own. */
+int lsn_corner_pool_forward(int mode, const float *x, int x_pitch, float *y, int y_pitch, int accumulate, int B, int H, int W, int C,
+                            lsn_stream_t stream);
+int lsn_corner_pool_backward(int mode, const float *x, int x_pitch, const float *grad_y, int gy_pitch, float *grad_x, int gx_pitch,
+                             int accumulate, int B, int H, int W, int C, lsn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

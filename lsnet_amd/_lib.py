@@ -121,6 +121,8 @@ EXPORTS = [
     'lsn_cross_iou_rows_forward', 'lsn_cross_iou_rows_backward',
     'lsn_assign_workspace_bytes', 'lsn_centroid_assign', 'lsn_centroid_assign_batch', 'lsn_atss_assign', 'lsn_atss_assign_batch',
     'lsn_dense_targets',
+    'lsn_pool_output_size', 'lsn_max_pool2d_forward', 'lsn_max_pool2d_backward', 'lsn_avg_pool2d_forward', 'lsn_avg_pool2d_backward',
+    'lsn_upsample_add_forward', 'lsn_upsample_add_backward', 'lsn_corner_pool_forward', 'lsn_corner_pool_backward',
 ]
 
 _lib = None

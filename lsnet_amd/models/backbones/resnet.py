@@ -15,7 +15,7 @@ from ...cnn import build_conv_layer, build_norm_layer, constant_init, kaiming_in
 from ...ops.batch_norm import bn_act
 from ...ops import resblock
 from ...ops.conv import conv_bn_act, conv_bn_act_frozen
-from ...ops.pool import avg_pool_nchw
+from ...ops.pool import avg_pool, max_pool
 from ..builder import BACKBONES
 
 
@@ -39,7 +39,7 @@ def _shortcut(downsample, x):
     mods = list(downsample)
     if isinstance(mods[-1], _BatchNorm):
         for m in mods[:-2]:
-            x = avg_pool_nchw(x, m) if isinstance(m, nn.AvgPool2d) else m(x)   # (avg_down shortcuts: ops/pool.py)
+            x = avg_pool(x, m) if isinstance(m, nn.AvgPool2d) else m(x)   # (avg_down shortcuts: ops/pool.py)
         if len(mods) >= 2:
             return _conv_bn(mods[-2], mods[-1], x, relu=False)
         return bn_act(mods[-1], x, relu=False)
@@ -308,7 +308,7 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         x = self.stem(x) if self.deep_stem else _conv_bn(self.conv1, self.norm1, x, relu=True)
-        x = self.maxpool(x)
+        x = max_pool(x, self.maxpool)
         outs = []
         for i, name in enumerate(self.res_layers):
             x = getattr(self, name)(x)

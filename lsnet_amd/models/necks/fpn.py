@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...cnn import ConvModule, xavier_init
+from ...ops.pool import max_pool2d, upsample_add
 from ..builder import NECKS
 
 
@@ -63,16 +64,12 @@ class FPN(nn.Module):
         lat = [conv(inputs[i + self.start_level]) for i, conv in enumerate(self.lateral_convs)]
         n = len(lat)
         for i in range(n - 1, 0, -1):  # top-down pathway
-            if 'scale_factor' in self.upsample_cfg:
-                up = F.interpolate(lat[i], **self.upsample_cfg)
-            else:
-                up = F.interpolate(lat[i], size=lat[i - 1].shape[2:], **self.upsample_cfg)
-            lat[i - 1] = lat[i - 1] + up
+            lat[i - 1] = upsample_add(lat[i], lat[i - 1], self.upsample_cfg)      # (ops/pool.py: one pass, one launch)
         outs = [self.fpn_convs[i](lat[i]) for i in range(n)]
         if self.num_outs > n:
             if not self.add_extra_convs:
                 for _ in range(self.num_outs - n):
-                    outs.append(F.max_pool2d(outs[-1], 1, stride=2))
+                    outs.append(max_pool2d(outs[-1], 1, stride=2))
             else:
                 src = {'on_input': inputs[self.backbone_end_level - 1], 'on_lateral': lat[-1],
                        'on_output': outs[-1]}[self.add_extra_convs]

@@ -49,6 +49,18 @@ def _pixel_pitch(t):
     return p
 
 
+def pool_pitch(t):
+    """Floats from one pixel to the next when `t` (B, C, H, W) is a dense channels-last tensor or a channel slice of one --
+    what the pooling entry points address by (base, pixel pitch) -- else None.  (Strides of extent-1 axes say nothing.)"""
+    if t.dim() != 4 or (t.shape[1] > 1 and t.stride(1) != 1) or t.numel() == 0:
+        return None
+    B, C, H, W = t.shape
+    p = t.stride(3) if W > 1 else t.stride(2) if H > 1 else t.stride(0) if B > 1 else C
+    if p < C or (W > 1 and t.stride(3) != p) or (H > 1 and t.stride(2) != W * p) or (B > 1 and t.stride(0) != H * W * p):
+        return None
+    return p
+
+
 def _strides(t):
     s = t.stride()
     return _lib.Strides4(s[0], s[1], s[2], s[3])
@@ -567,6 +579,108 @@ class HipBackend:
         out = torch.empty((P, D), dtype=torch.float32, device=table.device)
         _lib.check(lib.lsn_dense_targets(_ptr(gt_inds), P, _ptr(table), D, _ptr(out), _stream()))
         return out
+
+    # ------------------------------------------------------------------ pooling family (csrc/pool.hip), channels-last
+    CORNER_MODES = {'top': 0, 'bottom': 1, 'left': 2, 'right': 3}
+
+    @staticmethod
+    def _pool_arg(t, what):
+        p = pool_pitch(_f32(t, what))
+        if p is None:
+            raise ValueError(f'{what}: {tuple(t.shape)} with strides {t.stride()} is not (a channel slice of) a channels-last tensor')
+        return _ptr(t), p
+
+    @staticmethod
+    def _pool_new(like, shape):
+        return torch.empty(tuple(shape), device=like.device, dtype=torch.float32, memory_format=_CL)
+
+    @staticmethod
+    def pool_output_size(n, k, stride, pad, ceil_mode=False):
+        return _lib.load().lsn_pool_output_size(n, k, stride, pad, 1 if ceil_mode else 0)
+
+    def max_pool2d_forward(self, x, kernel, stride, pad, want_slot=True, out=None):
+        """x (B, C, H, W) channels-last (or a channel slice of such a tensor) -> (y, slot); slot: (B, Ho, Wo, C) uint8, the
+        winning window positions the backward needs (None when not wanted)."""
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        kh, kw = kernel
+        Ho, Wo = (self.pool_output_size(n, k, stride, pad) for n, k in ((H, kh), (W, kw)))
+        y = self._pool_new(x, (B, C, max(Ho, 1), max(Wo, 1))) if out is None else out
+        slot = torch.empty((B, max(Ho, 1), max(Wo, 1), C), device=x.device, dtype=torch.uint8) if want_slot else None
+        (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
+        _lib.check(lib.lsn_max_pool2d_forward(xp, xpitch, yp, ypitch, _ptr(slot), B, H, W, C, kh, kw, stride, pad, _stream()))
+        return y, slot
+
+    def max_pool2d_backward(self, grad_y, slot, x_shape, kernel, stride, pad, out=None):
+        lib = _lib.load()
+        B, C, H, W = x_shape
+        gx = self._pool_new(grad_y, x_shape) if out is None else out
+        (gp, gpitch), (xp, xpitch) = self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
+        _lib.check(lib.lsn_max_pool2d_backward(gp, gpitch, _ptr(slot), xp, xpitch, B, H, W, C, kernel[0], kernel[1], stride, pad,
+                                               _stream()))
+        return gx
+
+    def avg_pool2d_forward(self, x, kernel, stride, pad, ceil_mode, count_include_pad, out=None):
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        kh, kw = kernel
+        Ho, Wo = (self.pool_output_size(n, k, stride, pad, ceil_mode) for n, k in ((H, kh), (W, kw)))
+        y = self._pool_new(x, (B, C, max(Ho, 1), max(Wo, 1))) if out is None else out
+        (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
+        _lib.check(lib.lsn_avg_pool2d_forward(xp, xpitch, yp, ypitch, B, H, W, C, kh, kw, stride, pad, 1 if ceil_mode else 0,
+                                              1 if count_include_pad else 0, _stream()))
+        return y
+
+    def avg_pool2d_backward(self, grad_y, x_shape, kernel, stride, pad, ceil_mode, count_include_pad, out=None):
+        lib = _lib.load()
+        B, C, H, W = x_shape
+        gx = self._pool_new(grad_y, x_shape) if out is None else out
+        (gp, gpitch), (xp, xpitch) = self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
+        _lib.check(lib.lsn_avg_pool2d_backward(gp, gpitch, xp, xpitch, B, H, W, C, kernel[0], kernel[1], stride, pad,
+                                               1 if ceil_mode else 0, 1 if count_include_pad else 0, _stream()))
+        return gx
+
+    def upsample_add_forward(self, top, lat, out=None):
+        """lat + nearest-upsampled top, for lat of twice top's size (or one less, per axis); out may be lat itself."""
+        lib = _lib.load()
+        B, C, H, W = lat.shape
+        h, w = top.shape[2:]
+        out = self._pool_new(lat, lat.shape) if out is None else out
+        (tp, tpitch), (lp, lpitch), (op, opitch) = self._pool_arg(top, 'top'), self._pool_arg(lat, 'lat'), self._pool_arg(out, 'out')
+        _lib.check(lib.lsn_upsample_add_forward(tp, tpitch, lp, lpitch, op, opitch, B, h, w, H, W, C, _stream()))
+        return out
+
+    def upsample_add_backward(self, grad_out, top_shape, out=None, accumulate=False):
+        """The gradient of `top`; accumulate: added to what `out` holds."""
+        lib = _lib.load()
+        B, C, H, W = grad_out.shape
+        h, w = top_shape[2:]
+        assert out is not None or not accumulate
+        gt = self._pool_new(grad_out, top_shape) if out is None else out
+        (gp, gpitch), (tp, tpitch) = self._pool_arg(grad_out, 'grad_out'), self._pool_arg(gt, 'grad_top')
+        _lib.check(lib.lsn_upsample_add_backward(gp, gpitch, tp, tpitch, 1 if accumulate else 0, B, h, w, H, W, C, _stream()))
+        return gt
+
+    def corner_pool_forward(self, mode, x, out=None, accumulate=False):
+        """Running maximum of x towards the `mode` border ('top', 'bottom', 'left', 'right'); accumulate: added to `out`."""
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        assert out is not None or not accumulate
+        y = self._pool_new(x, x.shape) if out is None else out
+        (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
+        _lib.check(lib.lsn_corner_pool_forward(self.CORNER_MODES[mode], xp, xpitch, yp, ypitch, 1 if accumulate else 0, B, H, W, C,
+                                               _stream()))
+        return y
+
+    def corner_pool_backward(self, mode, x, grad_y, out=None, accumulate=False):
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        assert out is not None or not accumulate
+        gx = self._pool_new(x, x.shape) if out is None else out
+        (xp, xpitch), (gp, gpitch), (dp, dpitch) = self._pool_arg(x, 'x'), self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
+        _lib.check(lib.lsn_corner_pool_backward(self.CORNER_MODES[mode], xp, xpitch, gp, gpitch, dp, dpitch, 1 if accumulate else 0,
+                                                B, H, W, C, _stream()))
+        return gx
 
     # ------------------------------------------------------------------ LSHead's cumulative offset rescaling
     @staticmethod
