@@ -611,13 +611,13 @@ int lsn_debug_phase_clocks(long long *device_buf_512, int word);
 
 /* Per-kernel-family launch timing.  lsn_prof_enable(1) clears the log and makes every launch of the instrumented
  * families record a HIP event pair on its launch stream; lsn_prof_read() waits for the recorded events and returns one
- * entry per family -- dcn_fwd, dcn_bwd_data, dcn_wgrad, conv_fwd, conv_bwd_data, conv_wgrad, norm, gconv -- with the
+ * entry per family -- dcn_fwd, dcn_bwd_data, dcn_wgrad, conv_fwd, conv_bwd_data, conv_wgrad, norm, gconv, decode -- with the
  * launch count, the summed kernel time and the summed ALGORITHMIC flops / bytes of those launches (contractions: 2 x
  * output pixels x Co x C/groups x kh x kw flops; bytes: each operand read or written once).
  * lsn_prof_enable(on): 0 = off, 1 = every family, any other value = a bit mask of families in the order above (bit 0 =
  * dcn_fwd ...), so that a timed run can carry the events of ONE family only (a few dozen launches per step) after a
  * warm-up run with all of them found out which one dominates.
- * Returns the number of entries written (8) or a negative lsn error.  Not thread-safe. */
+ * Returns the number of entries written (9) or a negative lsn error.  Not thread-safe. */
 typedef struct lsn_prof_entry {
     char name[48];
     long long launches;
@@ -774,6 +774,38 @@ int lsn_corner_pool_forward(int mode, const float *x, int x_pitch, float *y, int
                             lsn_stream_t stream);
 int lsn_corner_pool_backward(int mode, const float *x, int x_pitch, const float *grad_y, int gy_pitch, float *grad_x, int gx_pitch,
                              int accumulate, int B, int H, int W, int C, lsn_stream_t stream);
+
+/* ---- detection decode (csrc/decode.hip; the arithmetic and the tie rule in csrc/decode_rows.h) -----------------------
+ * LSHead.get_bboxes for a batch in one call (lsnet_head.py:1439-1668, bbox_nms.py:60-99, nms_wrapper.py:119-157): per
+ * level the nms_pre points with the largest max-over-classes sigmoid score (equal scores to the lower point row, a NaN
+ * ranks largest and is no candidate); the selected points decoded -- (neg, pos) pairs to signed values, box from the
+ * landmark layout, * stride, + the point, clamp to the image, / the scale factors -- every operation separately rounded;
+ * a candidate per (point, class) with score > score_thr; candidates ordered by descending score, equal scores by ascending
+ * (level, point row, class); greedy NMS (suppressed when IoU > iou_thr) on box + label * (max_coordinate + 1), the maximum
+ * taken over the image's candidate boxes, offset 0 with class_agnostic; the first max_per_img kept are written.
+ *   levels: n_levels <= 8 of lsn_decode_level: maps (B, C, H, W) of logits, (B, cb, H, W) of the box source and (B, cv, H, W)
+ *     of the vector source (may be the same memory), each with its element strides (batch, channel, y, x), read in place;
+ *   kind 0 (bbox): box and the 8 vector columns [x_top, y1, x1, y_left, x_bottom, y2, x2, y_right] from a 20-channel
+ *     extreme-point map (num_vectors = 4); kind 1 (segm, pose_kbox): vectors from a 4 * (num_vectors + 1)-channel map, the
+ *     box their min / max; kind 2 (pose_bbox): box from the 20-channel map, vectors from the vector map;
+ *   img_hw (B, 2) = (img_h, img_w) and scale_factors (B, 4), HOST arrays, read before the call returns; 1.0 = no rescale;
+ *   nms_pre <= 0 or >= H * W takes every point of a level; B <= 64; 0 < max_per_img <= 2048;
+ *   outputs, device: dets (B, max_per_img, 5), vecs (B, max_per_img, 2 * num_vectors), labels (B, max_per_img) int64,
+ *     counts (B) int32: the rows written for image b; NEGATIVE when the image had more than cand_cap candidates (its rows
+ *     are undefined and the caller decodes it another way).
+ * Asynchronous on `stream`; allocates nothing and reads nothing back; the result does not depend on the order in which
+ * workgroups run (integer atomics only, and a total order of the candidates).  workspace: lsn_decode_workspace_bytes
+ * (the same B, levels' H and W, nms_pre and cand_cap; -1 for sizes out of range), 16-byte aligned. */
+typedef struct {
+    int H, W;
+    float stride;
+    const float *cls, *box, *vec;
+    int64_t cls_strides[4], box_strides[4], vec_strides[4];
+} lsn_decode_level;
+int64_t lsn_decode_workspace_bytes(int B, int n_levels, const lsn_decode_level *levels, int nms_pre, int cand_cap);
+int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C, const float *img_hw, const float *scale_factors,
+                     int num_vectors, int kind, int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img,
+                     int cand_cap, float *dets, float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream);
 
 #ifdef __cplusplus
 }

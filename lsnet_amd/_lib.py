@@ -83,6 +83,12 @@ class GateJob(ctypes.Structure):     # lsn_gate_job
                 ('per_image', ctypes.c_int64), ('gy_batch_stride', ctypes.c_int64)]
 
 
+class DecodeLevel(ctypes.Structure):     # lsn_decode_level
+    _fields_ = [('H', ctypes.c_int), ('W', ctypes.c_int), ('stride', ctypes.c_float),
+                ('cls', ctypes.c_void_p), ('box', ctypes.c_void_p), ('vec', ctypes.c_void_p),
+                ('cls_strides', ctypes.c_int64 * 4), ('box_strides', ctypes.c_int64 * 4), ('vec_strides', ctypes.c_int64 * 4)]
+
+
 class ProfEntry(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 48), ('launches', ctypes.c_longlong), ('total_ms', ctypes.c_double),
                 ('flops', ctypes.c_double), ('bytes', ctypes.c_double)]
@@ -123,6 +129,7 @@ EXPORTS = [
     'lsn_dense_targets',
     'lsn_pool_output_size', 'lsn_max_pool2d_forward', 'lsn_max_pool2d_backward', 'lsn_avg_pool2d_forward', 'lsn_avg_pool2d_backward',
     'lsn_upsample_add_forward', 'lsn_upsample_add_backward', 'lsn_corner_pool_forward', 'lsn_corner_pool_backward',
+    'lsn_decode_workspace_bytes', 'lsn_decode_batch',
 ]
 
 _lib = None
@@ -141,6 +148,11 @@ def load():
     lib.lsn_last_error.restype = ctypes.c_char_p
     lib.lsn_nms_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_assign_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_decode_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_decode_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DecodeLevel), ctypes.c_int, ctypes.c_int]
+    lib.lsn_decode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DecodeLevel), ctypes.c_int, c_float_p, c_float_p,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
     lib.lsn_group_norm_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_bn_eval_act_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_dcn_backward_workspace_bytes.restype = ctypes.c_int64
@@ -160,7 +172,7 @@ def check(rc):
         raise RuntimeError(msg)
 
 
-PROF_FAMILIES = ('dcn_fwd', 'dcn_bwd_data', 'dcn_wgrad', 'conv_fwd', 'conv_bwd_data', 'conv_wgrad', 'norm', 'gconv')
+PROF_FAMILIES = ('dcn_fwd', 'dcn_bwd_data', 'dcn_wgrad', 'conv_fwd', 'conv_bwd_data', 'conv_wgrad', 'norm', 'gconv', 'decode')
 
 
 def prof_enable(on, families=None):

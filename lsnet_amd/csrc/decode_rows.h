@@ -1,0 +1,157 @@
+// Row arithmetic of the detection decode -- LSHead.get_bboxes -> _get_bboxes_single -> multiclass_nms_lsvr -> batched_nms ->
+// nms of lsnet_amd/models/dense_heads/ls_head.py, core/post_processing.py and ops/nms.py (reference: lsnet_head.py:321-370,
+// 1439-1668, bbox_nms.py:60-99, nms_wrapper.py:119-157, nms_cpu.cpp:21-63) -- written once for the device kernels
+// (csrc/decode.hip) and, compiled by a host compiler, for the loop-nest check of tests/test_decode_host.py.
+//
+// Every coordinate operation is one separately rounded fp32 operation, in the order of the torch statements: no fused
+// multiply-add.  The host side is compiled with -ffp-contract=off; on the device every product that feeds an addition passes
+// through an opaque register barrier and csrc/build.py compiles decode.hip with -ffp-contract=off on top of that.  Division
+// is the correctly rounded one (hipcc's default; never build this with fast-math).  expf is glibc's on the host and the
+// device library's in the kernel: a score may differ from the framework's sigmoid in its last bits (a few ulp of 6e-8),
+// which is why the callers' inputs keep decisive scores further apart than that.
+//
+// The library's own tie rule (the reference leaves exact ties to an unstable sort): candidates are ordered by descending
+// score, equal scores by ascending (level, point row, class).  decode_order_key states it as one 64-bit word.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LSN_DHD __host__ __device__ __forceinline__
+#else
+#define LSN_DHD static inline
+#endif
+
+enum { DECODE_BBOX = 0, DECODE_VECTORS = 1, DECODE_POSE_BBOX = 2 };   // lsn_decode_batch's `kind`
+
+// a * b, rounded to fp32 before anything else uses it
+LSN_DHD float decode_mul(float a, float b)
+{
+    float p = a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(p));
+#endif
+    return p;
+}
+
+LSN_DHD float decode_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// Unsigned key whose order is the ascending order of the floats; NaN is 0xffffffff, above everything (torch.topk's order).
+LSN_DHD uint32_t decode_key(float v)
+{
+    union { float f; uint32_t u; } c;
+    c.f = v;
+    if (v != v) return 0xffffffffu;
+    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
+}
+
+LSN_DHD float decode_key_value(uint32_t key)
+{
+    union { float f; uint32_t u; } c;
+    c.u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    return c.f;
+}
+
+// Ascending order of this word = descending score, then ascending candidate id.  id = slot * C + class, where the slots of an
+// image run over the levels in order and, inside a level, over its selected point rows in ascending order: ascending id is
+// ascending (level, point row, class).
+LSN_DHD uint64_t decode_order_key(float score, uint32_t id) { return ((uint64_t)(~decode_key(score)) << 32) | id; }
+LSN_DHD float decode_order_score(uint64_t k) { return decode_key_value(~(uint32_t)(k >> 32)); }
+LSN_DHD uint32_t decode_order_id(uint64_t k) { return (uint32_t)k; }
+
+// _signed_pairs: (neg, pos) -> pos if pos > neg else -neg
+LSN_DHD float decode_signed(float neg, float pos) { return pos > neg ? pos : -neg; }
+
+// torch.clamp(v, 0, hi): a NaN stays a NaN
+LSN_DHD float decode_clamp(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
+
+// torch's min / max of a reduction: a NaN wins
+LSN_DHD float decode_min(float a, float b) { return (a != a || a < b) ? a : b; }
+LSN_DHD float decode_max(float a, float b) { return (a != a || a > b) ? a : b; }
+
+// one coordinate: value * stride + anchor, clamped to [0, hi], / scale
+LSN_DHD float decode_coord(float v, float stride, float anchor, float hi, float scale)
+{
+    return decode_clamp(decode_mul(v, stride) + anchor, hi) / scale;
+}
+
+// A strided view of one image's map: element (c, y, x) is at base[c * sc + y * sy + x * sx].
+struct DecodeMap {
+    const float *base;
+    int64_t sc, sy, sx;
+};
+LSN_DHD float decode_at(const DecodeMap &m, int c, int y, int x) { return m.base[c * m.sc + y * m.sy + x * m.sx]; }
+
+// signed value j of a point: channels (2j, 2j + 1).  Landmark m has y = value 2m, x = value 2m + 1.
+LSN_DHD float decode_value(const DecodeMap &m, int j, int y, int x)
+{
+    return decode_signed(decode_at(m, 2 * j, y, x), decode_at(m, 2 * j + 1, y, x));
+}
+
+struct DecodeGeom {
+    float stride, img_w, img_h;   // level stride, clamp bounds
+    float sf[4];                  // the image's scale factors (1 when rescale is off)
+};
+
+// The box of point (y, x): [x1, y1, x2, y2] after clamp and rescale.
+//   extreme-point map (20 channels, landmarks top, left, bottom, right, centre): [x_left, y_top, x_right, y_bottom]
+//   vector map (4 * (nv + 1) channels, the last landmark is the centre): min / max over the nv vectors
+LSN_DHD void decode_box(const DecodeMap &m, int from_vectors, int nv, int y, int x, const DecodeGeom &g, float *box)
+{
+    const float ax = (float)x * g.stride, ay = (float)y * g.stride;
+    float x1, y1, x2, y2;
+    if (!from_vectors) {
+        x1 = decode_value(m, 3, y, x), y1 = decode_value(m, 0, y, x);
+        x2 = decode_value(m, 7, y, x), y2 = decode_value(m, 4, y, x);
+    } else {
+        x1 = x2 = decode_value(m, 1, y, x), y1 = y2 = decode_value(m, 0, y, x);
+        for (int k = 1; k < nv; ++k) {
+            const float vy = decode_value(m, 2 * k, y, x), vx = decode_value(m, 2 * k + 1, y, x);
+            x1 = decode_min(x1, vx), x2 = decode_max(x2, vx), y1 = decode_min(y1, vy), y2 = decode_max(y2, vy);
+        }
+    }
+    box[0] = decode_coord(x1, g.stride, ax, g.img_w, g.sf[0]);
+    box[1] = decode_coord(y1, g.stride, ay, g.img_h, g.sf[1]);
+    box[2] = decode_coord(x2, g.stride, ax, g.img_w, g.sf[2]);
+    box[3] = decode_coord(y2, g.stride, ay, g.img_h, g.sf[3]);
+}
+
+// Column i of the output vectors of point (y, x).
+//   kind bbox: 8 columns [x_top, y1, x1, y_left, x_bottom, y2, x2, y_right], column i divided by sf[i % 4]; vmap is the
+//   extreme-point map and `box` the point's decoded box.
+//   otherwise: 2 nv columns, interleaved (x, y) of the vectors, x / sf[0] and y / sf[1]; vmap is the vector map.
+LSN_DHD float decode_vec(const DecodeMap &vmap, int kind, int i, int y, int x, const DecodeGeom &g, const float *box)
+{
+    const float ax = (float)x * g.stride, ay = (float)y * g.stride;
+    if (kind == DECODE_BBOX) {
+        switch (i) {
+        case 0: return decode_coord(decode_value(vmap, 1, y, x), g.stride, ax, g.img_w, g.sf[0]);   // x of top
+        case 1: return box[1];                                                                      // y1: / sf[1] already
+        case 2: return decode_coord(decode_value(vmap, 3, y, x), g.stride, ax, g.img_w, g.sf[2]);   // x1, / sf[2] here
+        case 3: return decode_coord(decode_value(vmap, 2, y, x), g.stride, ay, g.img_h, g.sf[3]);   // y of left
+        case 4: return decode_coord(decode_value(vmap, 5, y, x), g.stride, ax, g.img_w, g.sf[0]);   // x of bottom
+        case 5: return decode_coord(decode_value(vmap, 4, y, x), g.stride, ay, g.img_h, g.sf[1]);   // y2, / sf[1] here
+        case 6: return box[2];                                                                      // x2: / sf[2] already
+        default: return decode_coord(decode_value(vmap, 6, y, x), g.stride, ay, g.img_h, g.sf[3]);  // y of right
+        }
+    }
+    const int k = i >> 1;
+    if (i & 1) return decode_coord(decode_value(vmap, 2 * k, y, x), g.stride, ay, g.img_h, g.sf[1]);
+    return decode_coord(decode_value(vmap, 2 * k + 1, y, x), g.stride, ax, g.img_w, g.sf[0]);
+}
+
+// batched_nms's offset of a label: label * (max_coordinate + 1)
+LSN_DHD float decode_nms_offset(int label, float max_coordinate) { return decode_mul((float)label, max_coordinate + 1.f); }
+
+// nms's test: a suppresses b when their IoU exceeds thr (the operations of iou_gt in csrc/misc.hip, nms_cpu.cpp:21-63)
+LSN_DHD int decode_iou_gt(const float *a, const float *b, float thr)
+{
+    const float xx1 = fmaxf(a[0], b[0]), yy1 = fmaxf(a[1], b[1]);
+    const float xx2 = fminf(a[2], b[2]), yy2 = fminf(a[3], b[3]);
+    const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+    const float inter = decode_mul(w, h);
+    const float aa = decode_mul(a[2] - a[0], a[3] - a[1]);
+    const float ab = decode_mul(b[2] - b[0], b[3] - b[1]);
+    const float ovr = inter / (aa + ab - inter);
+    return ovr > thr;
+}

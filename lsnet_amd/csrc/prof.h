@@ -17,7 +17,8 @@ enum {
     PROF_CONV_WGRAD = 5,  // dense conv weight / bias gradient
     PROF_NORM = 6,        // frozen-BN + add + ReLU and GroupNorm passes (HBM-bound streaming kernels)
     PROF_GCONV = 7,       // grouped conv (ResNeXt)
-    PROF_N = 8
+    PROF_DECODE = 8,      // detection decode (select, candidates, sort + NMS: three launches per batch)
+    PROF_N = 9
 };
 
 struct ProfRec {

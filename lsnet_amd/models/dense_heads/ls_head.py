@@ -40,6 +40,13 @@ from ..builder import HEADS, build_loss
 FUSED_LEVEL_SUMS = os.environ.get('LSNET_FUSED_LEVEL_SUMS', '1') != '0'
 # LSNET_SIDE_STREAM_TARGETS=0: the init-stage targets on the main stream, between the head's forward and the loss (A/B switch)
 SIDE_STREAM_TARGETS = os.environ.get('LSNET_SIDE_STREAM_TARGETS', '1') != '0'
+# LSNET_NATIVE_DECODE=0: get_bboxes decodes with the torch statements on the device too (A/B switch; tools/README.md)
+NATIVE_DECODE = os.environ.get('LSNET_NATIVE_DECODE', '1') != '0'
+# candidates (point, class pairs above score_thr) per image the native decode has room for; an image with more is decoded
+# by the torch statements AFTER the native call has run, so it pays for both.  5 levels x nms_pre = 1000 points give at most
+# 5000 x C candidates.  The benchmark's inference leg (C = 1, shifted bias) has at most 3350 by construction; how many a
+# trained C = 80 detector produces per image has not been counted.
+DECODE_CAND_CAP = 16384
 
 # regression branches of each task; the LAST branch's offsets also drive the classification
 # PyramidDeformConv (lsnet_head.py:638, 653, 680, 695)
@@ -773,6 +780,31 @@ class LSHead(nn.Module):
                    rescale=False, nms=True):
         """lsnet_head.py:1439-1511: refine-stage vectors -> boxes + landmark vectors, per image
         top-k, decode and NMS."""
+        cfg = self.test_cfg if cfg is None else cfg
+        sources = self._decode_sources(bbox_pts_preds_refine, segm_pts_preds_refine, pose_pts_preds_refine)
+        padded, counts = None, [-1] * len(img_metas)       # a negative count: the image takes the torch statements
+        if nms and self._native_decode_ok(cls_scores, sources, cfg, len(img_metas)):
+            padded = self._decode_native(cls_scores, sources, img_metas, cfg, rescale)
+            counts = padded[3].cpu().tolist()               # the one host read of the batch
+        maps = points = None
+        results = []
+        for i, meta in enumerate(img_metas):
+            if counts[i] >= 0:
+                results.append(tuple(t[i, :counts[i]] for t in padded[:3]))
+                continue
+            if maps is None:
+                maps = self._dense_decode(bbox_pts_preds_refine, segm_pts_preds_refine, pose_pts_preds_refine)
+                device = cls_scores[0].device
+                points = [self.point_generators[l].grid_points(cls_scores[l].shape[-2:], self.point_strides[l], device)
+                          for l in range(len(cls_scores))]
+            results.append(self._get_bboxes_single([c[i].detach() for c in cls_scores],
+                                                   [m[i].detach() for m in maps[0]],
+                                                   [m[i].detach() for m in maps[1]], points, meta['img_shape'],
+                                                   meta['scale_factor'], cfg, rescale, nms))
+        return results
+
+    def _dense_decode(self, bbox_pts_preds_refine, segm_pts_preds_refine, pose_pts_preds_refine):
+        """The whole refine maps of every level -> (box maps, vector maps)."""
         if self.task in ('bbox', 'pose_bbox'):
             dec = [self.extreme_points2bbox(p, extreme=True) for p in bbox_pts_preds_refine]
             box_maps = [d[1] for d in dec]
@@ -785,16 +817,46 @@ class LSHead(nn.Module):
             vec_maps = [d[0] for d in dec]
             if self.task == 'pose_kbox':
                 box_maps = [d[1] for d in dec]
-        device = cls_scores[0].device
-        points = [self.point_generators[i].grid_points(cls_scores[i].shape[-2:], self.point_strides[i], device)
-                  for i in range(len(cls_scores))]
-        results = []
-        for i, meta in enumerate(img_metas):
-            results.append(self._get_bboxes_single([c[i].detach() for c in cls_scores],
-                                                   [m[i].detach() for m in box_maps],
-                                                   [m[i].detach() for m in vec_maps], points, meta['img_shape'],
-                                                   meta['scale_factor'], cfg, rescale, nms))
-        return results
+        return box_maps, vec_maps
+
+    def _decode_sources(self, bbox_refine, segm_refine, pose_refine):
+        """(box-source maps, vector-source maps) of the task, as the head produced them."""
+        if self.task == 'bbox':
+            return bbox_refine, bbox_refine
+        if self.task == 'segm':
+            return segm_refine, segm_refine
+        if self.task == 'pose_kbox':
+            return pose_refine, pose_refine
+        return bbox_refine, pose_refine
+
+    def _native_decode_ok(self, cls_scores, sources, cfg, num_imgs):
+        """The library decodes the batch in one call (lsn_decode_batch): fp32 device tensors, plain NMS, a positive
+        max_per_img, at most 64 images and 8 levels.  Everything else keeps the torch statements."""
+        if not NATIVE_DECODE or not cls_scores[0].is_cuda or not hasattr(get_backend(cls_scores[0]), 'decode_batch'):
+            return False
+        nms_cfg = dict(cfg.nms)
+        if nms_cfg.get('type', 'nms') != 'nms' or set(nms_cfg) - {'type', 'iou_thr', 'class_agnostic'} or 'iou_thr' not in nms_cfg:
+            return False
+        return 0 < cfg.max_per_img <= 2048 and 0 < num_imgs <= 64 and num_imgs == cls_scores[0].shape[0] and \
+            len(cls_scores) <= 8 and all(t.dtype == torch.float32 and t.is_cuda for maps in (cls_scores,) + tuple(sources) for t in maps)
+
+    def _decode_native(self, cls_scores, sources, img_metas, cfg, rescale):
+        box_src, vec_src = sources
+        backend = get_backend(cls_scores[0])
+        levels = [(c.detach(), b.detach(), v.detach(), self.point_strides[i])
+                  for i, (c, b, v) in enumerate(zip(cls_scores, box_src, vec_src))]
+        sfs = []
+        for meta in img_metas:
+            sf = np.ones(4, np.float32)             # x / 1.0f is exact: no rescale
+            if rescale:
+                sf = np.atleast_1d(np.asarray(meta['scale_factor'], dtype=np.float32))
+                sf = np.tile(sf, 4)[:4] if sf.size < 4 else sf
+            sfs.append(sf)
+        nms_cfg = cfg.nms
+        return backend.decode_batch(levels, [meta['img_shape'][:2] for meta in img_metas], sfs, self.num_vectors,
+                                    backend.DECODE_KINDS[self.task], cfg.get('nms_pre', -1), float(cfg.score_thr),
+                                    float(nms_cfg['iou_thr']), bool(nms_cfg.get('class_agnostic', False)),
+                                    int(cfg.max_per_img), DECODE_CAND_CAP)
 
     def _get_bboxes_single(self, cls_scores, bbox_preds, vec_preds, mlvl_points, img_shape, scale_factor, cfg,
                            rescale=False, nms=True):

@@ -471,6 +471,43 @@ class HipBackend:
                                _ptr(ws), _stream()))
         return keep[:int(num.item())]
 
+    # ------------------------------------------------------------------ detection decode
+    DECODE_KINDS = {'bbox': 0, 'segm': 1, 'pose_kbox': 1, 'pose_bbox': 2}
+
+    def decode_batch(self, levels, img_hw, scale_factors, num_vectors, kind, nms_pre, score_thr, iou_thr, class_agnostic,
+                     max_per_img, cand_cap):
+        """LSHead.get_bboxes for a batch in one call (lsn_decode_batch).  levels: (cls (B, C, H, W), box map, vector map,
+        stride) per level, float32 device tensors of any strides, read in place; img_hw / scale_factors: per image (h, w) and
+        four factors.  -> (dets (B, max_per_img, 5), vecs (B, max_per_img, 2 nv), labels (B, max_per_img) int64, counts (B,)
+        int32), all on the device: the first counts[b] rows of image b are its detections; a negative count means more
+        than cand_cap candidates -- that image's rows are undefined."""
+        lib = _lib.load()
+        B, C = levels[0][0].shape[:2]
+        dev = levels[0][0].device
+        arr = (_lib.DecodeLevel * len(levels))()
+        for lv, (cls, box, vec, stride) in zip(arr, levels):
+            for t, what in ((cls, 'cls'), (box, 'box map'), (vec, 'vector map')):
+                _f32(t, what)
+                if t.dim() != 4 or t.shape[0] != B or t.shape[2:] != cls.shape[2:] or t.device != dev:
+                    raise ValueError(f'decode_batch: {what} of shape {tuple(t.shape)} beside logits {tuple(cls.shape)}')
+            lv.H, lv.W, lv.stride = cls.shape[2], cls.shape[3], float(stride)
+            lv.cls, lv.box, lv.vec = cls.data_ptr(), box.data_ptr(), vec.data_ptr()
+            lv.cls_strides[:], lv.box_strides[:], lv.vec_strides[:] = cls.stride(), box.stride(), vec.stride()
+        hw = (ctypes.c_float * (2 * B))(*[float(v) for p in img_hw for v in p])
+        sf = (ctypes.c_float * (4 * B))(*[float(v) for p in scale_factors for v in p])
+        nbytes = int(lib.lsn_decode_workspace_bytes(B, len(levels), arr, int(nms_pre), int(cand_cap)))
+        if nbytes < 0:
+            _lib.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
+        vecs = torch.empty((B, max_per_img, 2 * num_vectors), dtype=torch.float32, device=dev)
+        labels = torch.empty((B, max_per_img), dtype=torch.int64, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.check(lib.lsn_decode_batch(B, len(levels), arr, C, hw, sf, int(num_vectors), int(kind), int(nms_pre), score_thr,
+                                        iou_thr, int(bool(class_agnostic)), int(max_per_img), int(cand_cap), dets.data_ptr(),
+                                        vecs.data_ptr(), labels.data_ptr(), counts.data_ptr(), ws.data_ptr(), _stream()))
+        return dets, vecs, labels, counts
+
     # ------------------------------------------------------------------ k nearest per column (assigners)
     def topk_columns(self, x, k, seg_start, seg_len, largest=False):
         """x (P, G) float32 on the device -> (values, indices), both (nseg * k, G): per row segment the k smallest
