@@ -807,6 +807,70 @@ int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C,
                      int num_vectors, int kind, int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img,
                      int cand_cap, float *dets, float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream);
 
+/* ---- corner-point verification: targets and losses of LSCPVHead (csrc/cpv.hip, arithmetic in csrc/cpv_rows.h) -------------
+ * Reference: point_hm_assigner.py:8-166, gaussian_focal_loss.py:8-89, smooth_l1_loss.py:8-90, focal_loss.py:45-71.
+ * Every call is asynchronous on `stream`, allocates nothing, reads nothing back, uses no atomic operation and gives the same
+ * bits on every run: sums go to fixed slots and are added in index order.
+ *
+ * lsn_corner_targets_batch: PointHMAssigner.assign_dense for B <= 64 images over the SAME points (P, 3) = x, y, stride.
+ *   valid: (B, P) uint8 or NULL (all valid); an invalid point is never picked and gets zero targets.  gt_bboxes / gt_offset
+ *   as the _assign_batch calls take them (host offsets, an image may have no gt: all its targets are 0).  For the top-left
+ *   (c = 0) and the bottom-right (c = 1) corner of every gt, on every level int(log2(stride)) in [0, 16) present among the
+ *   image's valid points, the nearest valid point (sqrt(dx^2 + dy^2), equal distances to the lowest row) is a positive:
+ *   hm = 1, off = (corner - xy) / 2^level, from the HIGHEST gt row that picked the point.  With gaussian_bump every other
+ *   valid point takes max over the image's gts of exp(-d^2 / (2 sigma^2)) where d < radius (gaussian_radius of the box at
+ *   overlap gaussian_iou, sigma = (2 radius + 1) / 6), else 0.  Outputs: hm (B, 2, P), off (B, 2, P, 2), npos (B, 2) int32
+ *   = positives per image and corner.  Two launches; no (P x G) matrix: workspace of
+ *   lsn_corner_targets_workspace_bytes(sum G) bytes.  P == 0 or no gt in the whole batch is LSN_ERR_INVALID.
+ *
+ * lsn_corner_loss_forward / _backward: the heat-map (GaussianFocalLoss on logits) and offset (SmoothL1Loss) losses of all
+ *   n_levels <= 8 levels.  lsn_corner_level: the (B, 2, H, W) score and (B, 4, H, W) offset maps (channels: tl, br /
+ *   tl x, tl y, br x, br y) with their element strides, read in place; point row of cell (y, x) of level l =
+ *   sum_{k < l} H_k W_k + y W_l + x, the levels together hold P points.  hm / off / valid / npos as above.
+ *   loss_heat[l] = (S_tl / n_tl + S_br / n_br) / 2 with n_c = sum_b max(npos[b, c], 1), S_c the sum over the level's valid
+ *   points; loss_off alike over the positives (hm == 1) and both coordinates.  Forward: two launches, workspace of
+ *   lsn_corner_loss_workspace_bytes bytes (8-byte aligned).  Backward: g_heat / g_off (n_levels) upstream gradients in device
+ *   memory; writes every element of grad_score / grad_offset (shapes of score / offset, strides of their own, no two
+ *   elements at one address) once, one launch.
+ *
+ * lsn_sep_focal_forward / _backward: SEPFocalLoss over n_levels <= 8 maps of (B, C, H, W) logits against the contiguous
+ *   (B, C, h, w) maps `target` / `weight` read through F.interpolate's nearest rule (src = min(int(floorf(dst * ((float)in /
+ *   out))), in - 1)), no interpolated copy.  loss[0] = sum_pos / sum_pos(w) (0 without positives) + sum_neg / count(target > 0);
+ *   positives target == 1, negatives target < 1; a zero count divides as it does in fp32 arithmetic.  stats (4 floats,
+ *   device): what backward needs of the sums.  Forward two launches, workspace lsn_sep_focal_workspace_bytes; backward
+ *   (g: 1 upstream gradient, device) one launch that writes every element of the levels' `grad` (strides of its own). */
+typedef struct {
+    int H, W;
+    const float *score, *offset;
+    int64_t score_strides[4], offset_strides[4];
+    float *grad_score, *grad_offset;       /* backward only, as are their strides */
+    int64_t grad_score_strides[4], grad_offset_strides[4];
+} lsn_corner_level;
+typedef struct {
+    int H, W;
+    const float *logits;
+    int64_t strides[4];
+    float *grad;                           /* backward only, as are its strides */
+    int64_t grad_strides[4];
+} lsn_sem_level;
+int64_t lsn_corner_targets_workspace_bytes(int G);
+int lsn_corner_targets_batch(const float *points, int P, const uint8_t *valid, const float *gt_bboxes, int B,
+                             const int *gt_offset, int gaussian_bump, double gaussian_iou, float *hm, float *off,
+                             int32_t *npos, void *workspace, lsn_stream_t stream);
+int64_t lsn_corner_loss_workspace_bytes(int B, int n_levels, const lsn_corner_level *levels);
+int lsn_corner_loss_forward(int B, int P, int n_levels, const lsn_corner_level *levels, const float *hm, const float *off,
+                            const uint8_t *valid, const int32_t *npos, float alpha, float gamma, float beta,
+                            float *loss_heat, float *loss_off, void *workspace, lsn_stream_t stream);
+int lsn_corner_loss_backward(int B, int P, int n_levels, const lsn_corner_level *levels, const float *hm, const float *off,
+                             const uint8_t *valid, const int32_t *npos, float alpha, float gamma, float beta,
+                             const float *g_heat, const float *g_off, lsn_stream_t stream);
+int64_t lsn_sep_focal_workspace_bytes(int B, int C, int n_levels, const lsn_sem_level *levels);
+int lsn_sep_focal_forward(int B, int C, int n_levels, const lsn_sem_level *levels, const float *target, const float *weight,
+                          int h, int w, float gamma, float alpha, float *loss, float *stats, void *workspace,
+                          lsn_stream_t stream);
+int lsn_sep_focal_backward(int B, int C, int n_levels, const lsn_sem_level *levels, const float *target, const float *weight,
+                           int h, int w, float gamma, float alpha, const float *stats, const float *g, lsn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

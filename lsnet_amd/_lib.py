@@ -89,6 +89,18 @@ class DecodeLevel(ctypes.Structure):     # lsn_decode_level
                 ('cls_strides', ctypes.c_int64 * 4), ('box_strides', ctypes.c_int64 * 4), ('vec_strides', ctypes.c_int64 * 4)]
 
 
+class CornerLevel(ctypes.Structure):     # lsn_corner_level
+    _fields_ = [('H', ctypes.c_int), ('W', ctypes.c_int), ('score', ctypes.c_void_p), ('offset', ctypes.c_void_p),
+                ('score_strides', ctypes.c_int64 * 4), ('offset_strides', ctypes.c_int64 * 4),
+                ('grad_score', ctypes.c_void_p), ('grad_offset', ctypes.c_void_p),
+                ('grad_score_strides', ctypes.c_int64 * 4), ('grad_offset_strides', ctypes.c_int64 * 4)]
+
+
+class SemLevel(ctypes.Structure):     # lsn_sem_level
+    _fields_ = [('H', ctypes.c_int), ('W', ctypes.c_int), ('logits', ctypes.c_void_p), ('strides', ctypes.c_int64 * 4),
+                ('grad', ctypes.c_void_p), ('grad_strides', ctypes.c_int64 * 4)]
+
+
 class ProfEntry(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 48), ('launches', ctypes.c_longlong), ('total_ms', ctypes.c_double),
                 ('flops', ctypes.c_double), ('bytes', ctypes.c_double)]
@@ -130,6 +142,9 @@ EXPORTS = [
     'lsn_pool_output_size', 'lsn_max_pool2d_forward', 'lsn_max_pool2d_backward', 'lsn_avg_pool2d_forward', 'lsn_avg_pool2d_backward',
     'lsn_upsample_add_forward', 'lsn_upsample_add_backward', 'lsn_corner_pool_forward', 'lsn_corner_pool_backward',
     'lsn_decode_workspace_bytes', 'lsn_decode_batch',
+    'lsn_corner_targets_workspace_bytes', 'lsn_corner_targets_batch', 'lsn_corner_loss_workspace_bytes',
+    'lsn_corner_loss_forward', 'lsn_corner_loss_backward', 'lsn_sep_focal_workspace_bytes', 'lsn_sep_focal_forward',
+    'lsn_sep_focal_backward',
 ]
 
 _lib = None
@@ -153,6 +168,17 @@ def load():
     lib.lsn_decode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DecodeLevel), ctypes.c_int, c_float_p, c_float_p,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    lib.lsn_corner_targets_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_corner_targets_batch.argtypes = [vp, ci, vp, vp, ci, ctypes.POINTER(ci), ci, ctypes.c_double, vp, vp, vp, vp, vp]
+    lib.lsn_corner_loss_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_corner_loss_workspace_bytes.argtypes = [ci, ci, ctypes.POINTER(CornerLevel)]
+    lib.lsn_corner_loss_forward.argtypes = [ci, ci, ci, ctypes.POINTER(CornerLevel), vp, vp, vp, vp, cf, cf, cf, vp, vp, vp, vp]
+    lib.lsn_corner_loss_backward.argtypes = [ci, ci, ci, ctypes.POINTER(CornerLevel), vp, vp, vp, vp, cf, cf, cf, vp, vp, vp]
+    lib.lsn_sep_focal_workspace_bytes.restype = ctypes.c_int64
+    lib.lsn_sep_focal_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(SemLevel)]
+    lib.lsn_sep_focal_forward.argtypes = [ci, ci, ci, ctypes.POINTER(SemLevel), vp, vp, ci, ci, cf, cf, vp, vp, vp, vp]
+    lib.lsn_sep_focal_backward.argtypes = [ci, ci, ci, ctypes.POINTER(SemLevel), vp, vp, ci, ci, cf, cf, vp, vp, vp]
     lib.lsn_group_norm_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_bn_eval_act_workspace_bytes.restype = ctypes.c_int64
     lib.lsn_dcn_backward_workspace_bytes.restype = ctypes.c_int64

@@ -223,7 +223,12 @@ class PointHMAssigner:
 
     `assign_dense` is the form the head uses: targets and a positive MASK, no index lists, no host reads when the
     level strides are passed in.  `assign` is the reference's interface on top of it.  Where several gts pick the
-    same point the last gt's offset stays, as with the reference's sequential CPU indexing."""
+    same point the last gt's offset stays, as with the reference's sequential CPU indexing.
+
+    On the device (fp32) the targets of a whole batch are two launches of the library (`lsn_corner_targets_batch`:
+    csrc/cpv.hip, arithmetic in csrc/cpv_rows.h) -- `assign_dense_batch`, which `assign_dense` / `assign` go through too; the
+    torch statements below stay as they are: the checker of those kernels and the path of host tensors, other dtypes and
+    LSNET_NATIVE_CPV=0."""
 
     def __init__(self, gaussian_bump=False, gaussian_iou=0.7):
         self.gaussian_bump, self.gaussian_iou = gaussian_bump, gaussian_iou
@@ -264,6 +269,10 @@ class PointHMAssigner:
         if P == 0 or G == 0:
             z = points.new_zeros
             return z((P,), dtype=dtype), z((P, 2), dtype=torch.float32), z((P,), dtype=dtype), z((P, 2), dtype=torch.float32)
+        batch = self.assign_dense_batch(points, None, [gt_bboxes])
+        if batch is not None:
+            hm, off, _ = batch
+            return hm[0, 0], off[0, 0], hm[0, 1], off[0, 1]
         xy = points[:, :2]
         lvl = torch.log2(points[:, 2]).int()
         if strides is None:
@@ -279,6 +288,21 @@ class PointHMAssigner:
         hm_tl, off_tl = self._corner(xy, lvl, levels, gt_bboxes[:, :2], radius, sigma, dtype)
         hm_br, off_br = self._corner(xy, lvl, levels, gt_bboxes[:, 2:], radius, sigma, dtype)
         return hm_tl, off_tl, hm_br, off_br
+
+    def assign_dense_batch(self, points, valid, gt_bboxes):
+        """All images of a batch over the SAME points in one call of the library.  valid: (B, P) bool or None -- a point
+        that is not valid for an image is never picked and gets zero targets (the `inside` flags of a ragged batch);
+        gt_bboxes: per-image list, an image may have no gt.  -> (hm (B, 2, P), off (B, 2, P, 2), npos (B, 2) int32), corner 0
+        = top-left and 1 = bottom-right, hm long without `gaussian_bump`; or None when the kernels do not take the inputs
+        (the caller then assigns image by image).  The levels are the int(log2(stride)) present among the points."""
+        from ..ops.cpv_loss import MAX_IMAGES, native_ok
+        if points.shape[0] == 0 or sum(g.shape[0] for g in gt_bboxes) == 0 or len(gt_bboxes) > MAX_IMAGES or \
+                not native_ok(points, *gt_bboxes) or (valid is not None and not valid.is_cuda):
+            return None
+        from ..ops.backend import get_backend
+        hm, off, npos = get_backend(points).corner_targets_batch(points[:, :3], valid, gt_bboxes, self.gaussian_bump,
+                                                                 self.gaussian_iou)
+        return (hm if self.gaussian_bump else hm.long()), off, npos
 
     def assign(self, points, gt_bboxes, gt_labels=None):
         hm_tl, off_tl, hm_br, off_br = self.assign_dense(points, gt_bboxes)

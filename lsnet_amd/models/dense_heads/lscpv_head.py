@@ -15,18 +15,25 @@ cross-IOU losses) it adds, per FPN level:
 
 Same parameter names / shapes and outputs as the reference.  Everything the bbox task shares with `LSHead` IS
 `LSHead` (targets, cross-IOU loss evaluation over concatenated levels, the accumulating offset rescale of the pyramid
-gather); the additions follow its rules: level-batched launches, no data-dependent shapes in the training step."""
+gather); the additions follow its rules: level-batched launches, no data-dependent shapes in the training step.
+
+The targets and the three losses of the additions run as kernels of the library (csrc/cpv.hip: `lsn_corner_targets_batch`,
+`lsn_corner_loss_*`, `lsn_sep_focal_*`) when the tensors are fp32 on the device and the configured losses are exactly
+GaussianFocalLoss / SmoothL1Loss / SEPFocalLoss with reduction 'mean'; everything else -- host tensors, other dtypes,
+other losses, LSNET_NATIVE_CPV=0 -- runs the torch statements below, which are also the checker of those kernels."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ...cnn import ConvModule, bias_init_with_prob, normal_init
 from ...core import build_assigner, multiclass_nms
-from ...ops import PyramidDeformConv
+from ...core.assigners import PointHMAssigner
+from ...ops import PyramidDeformConv, cpv_loss
 from ...ops.conv import Conv2d
 from ...ops.corner_pool import BRPool, TLPool
 from ...ops.group_norm import GroupNorm
 from ..builder import HEADS, build_loss
+from ..losses.cpv_losses import GaussianFocalLoss, SEPFocalLoss, SmoothL1Loss
 from .ls_head import DCNConvModule, LSHead
 
 
@@ -194,9 +201,34 @@ class LSCPVHead(LSHead):
                          gt_bboxes_ignore=gt_bboxes_ignore)
 
     # --------------------------------------------------------------------------------------- loss
+    def get_hm_targets_native(self, flat_points, flat_flags, all_valid, gt_bboxes):
+        """The targets of the whole batch from the library, two launches: -> (hm (B, 2, N_all), off (B, 2, N_all, 2), valid
+        (B, N_all) bool or None, npos (B, 2) int32), corner 0 = top-left and 1 = bottom-right, hm float; or None when the
+        kernels do not take the inputs."""
+        if type(self.hm_assigner) is not PointHMAssigner:
+            return None
+        valid = None if all_valid else torch.stack(list(flat_flags), 0)
+        out = self.hm_assigner.assign_dense_batch(flat_points, valid, gt_bboxes)
+        if out is None:
+            return None
+        hm, off, npos = out
+        return hm.float(), off, valid, npos
+
     def get_hm_targets(self, flat_points, flat_flags, all_valid, gt_bboxes):
         """Corner heat-map / offset targets for every image over ALL points (lscpvnet_head.py:559-668 written
         densely): dict of (B, N_all[, 2]) tensors + the positive counts sum_img max(n_pos, 1) as device scalars."""
+        native = self.get_hm_targets_native(flat_points, flat_flags, all_valid, gt_bboxes)
+        if native is not None:
+            hm, off, valid, npos = native
+            out = {}
+            for i, c in enumerate(('tl', 'br')):
+                pos = hm[:, i] == 1
+                live = torch.ones_like(pos) if valid is None else valid.bool()
+                out[f'hm_{c}'], out[f'off_{c}'] = hm[:, i], off[:, i]
+                out[f'hm_w_{c}'] = live.float()
+                out[f'off_w_{c}'] = pos.float().unsqueeze(2).expand(-1, -1, 2)
+            n = npos.clamp(min=1).sum(0)
+            return out, n[0], n[1]
         per_img = []
         for i, boxes in enumerate(gt_bboxes):
             inside = None if all_valid else flat_flags[i]
@@ -221,6 +253,16 @@ class LSCPVHead(LSHead):
         n_br = sum(t['n_br'].clamp(min=1) for t in per_img)
         return out, n_tl, n_br
 
+    def _native_losses(self, hm_scores, hm_offsets, sem_scores, gt_sem_map, gt_sem_weights):
+        """The corner and semantic losses can run as the library's kernels: fp32 on the device, the three loss classes as
+        configured by default (their arithmetic is what the kernels state), at most 8 levels and 64 images."""
+        return type(self.loss_heatmap) is GaussianFocalLoss and type(self.loss_offset) is SmoothL1Loss and \
+            type(self.loss_sem) is SEPFocalLoss and \
+            all(l.reduction == 'mean' for l in (self.loss_heatmap, self.loss_offset, self.loss_sem)) and \
+            len(hm_scores) <= cpv_loss.MAX_LEVELS and hm_scores[0].shape[0] <= cpv_loss.MAX_IMAGES and \
+            gt_sem_map.shape == gt_sem_weights.shape and \
+            cpv_loss.native_ok(gt_sem_map, gt_sem_weights, *hm_scores, *hm_offsets, *sem_scores)
+
     def loss(self, cls_scores, bbox_pts_preds_init, bbox_pts_preds_refine, hm_scores, hm_offsets, sem_scores,
              gt_bboxes, gt_extremes, gt_sem_map, gt_sem_weights, gt_labels, img_metas, gt_bboxes_ignore=None):
         """lscpvnet_head.py:670-903: the bbox-task losses of LSHead + corner heat-map, corner offset and semantic
@@ -232,8 +274,19 @@ class LSCPVHead(LSHead):
         featmap_sizes = [tuple(m.shape[-2:]) for m in cls_scores]
         points, flags, all_valid = self.get_points(featmap_sizes, img_metas, device)
         num_level = [p.shape[0] for p in points]
-        tg, n_tl, n_br = self.get_hm_targets(torch.cat(points), [torch.cat(f) for f in flags], all_valid, gt_bboxes)
         assert cls_scores[0].shape[0] == gt_sem_map.shape[0] == len(gt_bboxes)
+        if self._native_losses(hm_scores, hm_offsets, sem_scores, gt_sem_map, gt_sem_weights):
+            native = self.get_hm_targets_native(torch.cat(points), [torch.cat(f) for f in flags], all_valid, gt_bboxes)
+            if native is not None:
+                hm, off, valid, npos = native
+                heat, offs = cpv_loss.corner_losses(hm_scores, hm_offsets, hm, off, valid, npos, self.loss_heatmap.alpha,
+                                                    self.loss_heatmap.gamma, self.loss_offset.beta)
+                out['loss_heatmap'] = list((self.loss_heatmap.loss_weight * heat).unbind(0))
+                out['loss_offset'] = list((self.loss_offset.loss_weight * offs).unbind(0))
+                out['loss_sem'] = self.loss_sem.loss_weight * cpv_loss.sep_focal_loss(
+                    sem_scores, gt_sem_map, gt_sem_weights, self.loss_sem.gamma, self.loss_sem.alpha)
+                return out
+        tg, n_tl, n_br = self.get_hm_targets(torch.cat(points), [torch.cat(f) for f in flags], all_valid, gt_bboxes)
 
         def levels(t):
             return torch.split(t, num_level, dim=1)

@@ -61,6 +61,18 @@ def pool_pitch(t):
     return p
 
 
+def _writable(t):
+    """a gradient buffer the kernels may write through its strides: fp32 and dense (no two elements at one address)"""
+    if t.dtype != torch.float32:
+        return False
+    expect = 1
+    for st, n in sorted((st, n) for st, n in zip(t.stride(), t.shape) if n > 1):
+        if st != expect:
+            return False
+        expect *= n
+    return True
+
+
 def _strides(t):
     s = t.stride()
     return _lib.Strides4(s[0], s[1], s[2], s[3])
@@ -616,6 +628,152 @@ class HipBackend:
         out = torch.empty((P, D), dtype=torch.float32, device=table.device)
         _lib.check(lib.lsn_dense_targets(_ptr(gt_inds), P, _ptr(table), D, _ptr(out), _stream()))
         return out
+
+    # ------------------------------------------------------------------ corner-point verification (csrc/cpv.hip)
+    @staticmethod
+    def _u8(valid, shape, dev):
+        if valid is None:
+            return None
+        if valid.dtype == torch.bool:
+            valid = valid.contiguous().view(torch.uint8)
+        if valid.dtype != torch.uint8 or tuple(valid.shape) != tuple(shape) or valid.device != dev:
+            raise TypeError(f'valid must be a bool / uint8 tensor of shape {tuple(shape)} beside the points')
+        return valid.contiguous()
+
+    def corner_targets_batch(self, points, valid, gt_bboxes, gaussian_bump, gaussian_iou, out=None):
+        """PointHMAssigner.assign_dense for the B images of a batch over the SAME points (P, 3) in two launches
+        (lsn_corner_targets_batch).  valid: (B, P) bool / uint8 or None; gt_bboxes: list of B (G_b, 4) tensors, an image may
+        have none.  -> hm (B, 2, P) float32, off (B, 2, P, 2), npos (B, 2) int32; corner 0 = top-left, 1 = bottom-right.
+        `out`: preallocated (hm, off, npos, workspace) for callers that must not allocate."""
+        lib = _lib.load()
+        points = _f32(points, 'points')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f'points must be (P, 3), got {tuple(points.shape)}')
+        points = points.contiguous()
+        P, B, dev = points.shape[0], len(gt_bboxes), points.device
+        gts, offs, G = self._assign_gts([g[:, :4] for g in gt_bboxes], 'gt_bboxes')
+        valid = self._u8(valid, (B, P), dev)
+        nbytes = int(lib.lsn_corner_targets_workspace_bytes(G))
+        if out is None:
+            hm = torch.empty((B, 2, P), dtype=torch.float32, device=dev)
+            off = torch.empty((B, 2, P, 2), dtype=torch.float32, device=dev)
+            npos = torch.empty((B, 2), dtype=torch.int32, device=dev)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        else:
+            hm, off, npos, ws = out
+            assert ws.numel() >= nbytes and hm.numel() == B * 2 * P and off.numel() == B * 4 * P and npos.numel() == B * 2
+            assert hm.is_contiguous() and off.is_contiguous() and npos.is_contiguous() and npos.dtype == torch.int32
+            _f32(hm, 'hm'), _f32(off, 'off')
+        _lib.check(lib.lsn_corner_targets_batch(_ptr(points), P, _ptr(valid), _ptr(gts), B, offs, int(bool(gaussian_bump)),
+                                                float(gaussian_iou), _ptr(hm), _ptr(off), _ptr(npos), _ptr(ws), _stream()))
+        return hm, off, npos
+
+    def _corner_args(self, scores, offsets, hm, off, valid, npos, grads=None):
+        B, dev = scores[0].shape[0], scores[0].device
+        arr = (_lib.CornerLevel * len(scores))()
+        P = 0
+        for i, (lv, s, o) in enumerate(zip(arr, scores, offsets)):
+            _f32(s, 'corner scores'), _f32(o, 'corner offsets')
+            if s.dim() != 4 or s.shape[:2] != (B, 2) or tuple(o.shape) != (B, 4) + tuple(s.shape[2:]) or o.device != dev:
+                raise ValueError(f'corner loss: level {i} has scores {tuple(s.shape)} and offsets {tuple(o.shape)}')
+            lv.H, lv.W = s.shape[2], s.shape[3]
+            lv.score, lv.offset = s.data_ptr(), o.data_ptr()
+            lv.score_strides[:], lv.offset_strides[:] = s.stride(), o.stride()
+            if grads is not None:
+                gs, go = grads[0][i], grads[1][i]
+                assert gs.shape == s.shape and go.shape == o.shape and _writable(gs) and _writable(go)
+                lv.grad_score, lv.grad_offset = gs.data_ptr(), go.data_ptr()
+                lv.grad_score_strides[:], lv.grad_offset_strides[:] = gs.stride(), go.stride()
+            P += lv.H * lv.W
+        _f32(hm, 'hm'), _f32(off, 'off')
+        if tuple(hm.shape) != (B, 2, P) or tuple(off.shape) != (B, 2, P, 2) or tuple(npos.shape) != (B, 2) or \
+                npos.dtype != torch.int32 or not (hm.is_contiguous() and off.is_contiguous() and npos.is_contiguous()):
+            raise ValueError(f'corner loss: targets {tuple(hm.shape)} / {tuple(off.shape)} / {tuple(npos.shape)} for {B} images '
+                             f'of {P} points')
+        return arr, B, P, self._u8(valid, (B, P), dev)
+
+    def corner_loss_forward(self, scores, offsets, hm, off, valid, npos, alpha, gamma, beta, out=None):
+        """Corner heat-map (Gaussian focal, on logits) and offset (smooth L1) losses of all levels in two launches.  scores /
+        offsets: per level (B, 2, H, W) / (B, 4, H, W), any strides; hm / off / npos / valid: corner_targets_batch's.
+        -> (loss_heat (L,), loss_off (L,)), each (S_tl / n_tl + S_br / n_br) / 2.  `out`: (loss_heat, loss_off, workspace)."""
+        lib = _lib.load()
+        arr, B, P, valid = self._corner_args(scores, offsets, hm, off, valid, npos)
+        dev, L = hm.device, len(scores)
+        nbytes = int(lib.lsn_corner_loss_workspace_bytes(B, L, arr))
+        if out is None:
+            heat = torch.empty(L, dtype=torch.float32, device=dev)
+            offl = torch.empty(L, dtype=torch.float32, device=dev)
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        else:
+            heat, offl, ws = out
+            assert ws.numel() * ws.element_size() >= nbytes and heat.numel() == L and offl.numel() == L
+        _lib.check(lib.lsn_corner_loss_forward(B, P, L, arr, _ptr(hm), _ptr(off), _ptr(valid), _ptr(npos), alpha, gamma, beta,
+                                               _ptr(heat), _ptr(offl), _ptr(ws), _stream()))
+        return heat, offl
+
+    def corner_loss_backward(self, scores, offsets, hm, off, valid, npos, alpha, gamma, beta, g_heat, g_off, out=None):
+        """-> (grad_scores, grad_offsets), lists of dense tensors in the maps' memory order, every element written, one launch.
+        g_heat / g_off: (L,) upstream gradients on the device.  `out`: preallocated (grad_scores, grad_offsets)."""
+        lib = _lib.load()
+        grads = out if out is not None else ([torch.empty_like(s) for s in scores], [torch.empty_like(o) for o in offsets])
+        arr, B, P, valid = self._corner_args(scores, offsets, hm, off, valid, npos, grads)
+        g_heat, g_off = _f32(g_heat, 'g_heat').contiguous(), _f32(g_off, 'g_off').contiguous()
+        assert g_heat.numel() == len(scores) and g_off.numel() == len(scores)
+        _lib.check(lib.lsn_corner_loss_backward(B, P, len(scores), arr, _ptr(hm), _ptr(off), _ptr(valid), _ptr(npos), alpha,
+                                                gamma, beta, _ptr(g_heat), _ptr(g_off), _stream()))
+        return grads
+
+    @staticmethod
+    def _sem_args(logits, target, weight, grads=None):
+        B, C = logits[0].shape[:2]
+        dev = logits[0].device
+        _f32(target, 'gt_sem_map'), _f32(weight, 'gt_sem_weights')
+        if target.dim() != 4 or target.shape[:2] != (B, C) or weight.shape != target.shape or target.device != dev or \
+                weight.device != dev:
+            raise ValueError(f'sep focal: semantic maps {tuple(target.shape)} / {tuple(weight.shape)} beside logits of '
+                             f'{B} x {C} maps')
+        arr = (_lib.SemLevel * len(logits))()
+        for i, (lv, x) in enumerate(zip(arr, logits)):
+            _f32(x, 'semantic logits')
+            if x.dim() != 4 or x.shape[:2] != (B, C) or x.device != dev:
+                raise ValueError(f'sep focal: level {i} has logits {tuple(x.shape)}')
+            lv.H, lv.W, lv.logits = x.shape[2], x.shape[3], x.data_ptr()
+            lv.strides[:] = x.stride()
+            if grads is not None:
+                assert grads[i].shape == x.shape and _writable(grads[i])
+                lv.grad = grads[i].data_ptr()
+                lv.grad_strides[:] = grads[i].stride()
+        return arr, B, C, target.contiguous(), weight.contiguous()
+
+    def sep_focal_forward(self, logits, target, weight, gamma, alpha, out=None):
+        """SEPFocalLoss over the per-level (B, C, H, W) logits against the (B, C, h, w) maps read through the nearest rule of
+        F.interpolate, two launches.  -> (loss (1,), stats (4,)): sum_pos / sum_pos(w) + sum_neg / count(target > 0) and what
+        backward needs.  `out`: preallocated (loss, stats, workspace)."""
+        lib = _lib.load()
+        arr, B, C, target, weight = self._sem_args(logits, target, weight)
+        dev = target.device
+        nbytes = int(lib.lsn_sep_focal_workspace_bytes(B, C, len(logits), arr))
+        if out is None:
+            loss = torch.empty(1, dtype=torch.float32, device=dev)
+            stats = torch.empty(4, dtype=torch.float32, device=dev)
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        else:
+            loss, stats, ws = out
+            assert ws.numel() * ws.element_size() >= nbytes and loss.numel() == 1 and stats.numel() == 4
+        _lib.check(lib.lsn_sep_focal_forward(B, C, len(logits), arr, _ptr(target), _ptr(weight), target.shape[2], target.shape[3],
+                                             gamma, alpha, _ptr(loss), _ptr(stats), _ptr(ws), _stream()))
+        return loss, stats
+
+    def sep_focal_backward(self, logits, target, weight, gamma, alpha, stats, g, out=None):
+        """-> list of dense gradients in the logits' memory order, every element written, one launch.  g: the upstream
+        gradient (1 element, device).  `out`: the preallocated gradients."""
+        lib = _lib.load()
+        grads = out if out is not None else [torch.empty_like(x) for x in logits]
+        arr, B, C, target, weight = self._sem_args(logits, target, weight, grads)
+        g = _f32(g, 'g').reshape(1).contiguous()
+        _lib.check(lib.lsn_sep_focal_backward(B, C, len(logits), arr, _ptr(target), _ptr(weight), target.shape[2],
+                                              target.shape[3], gamma, alpha, _ptr(stats), _ptr(g), _stream()))
+        return grads
 
     # ------------------------------------------------------------------ pooling family (csrc/pool.hip), channels-last
     CORNER_MODES = {'top': 0, 'bottom': 1, 'left': 2, 'right': 3}
