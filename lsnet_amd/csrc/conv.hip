@@ -692,7 +692,10 @@ static int prepare_weights(int kind, const float *w, void *prepared, int C, int 
                            int dil, hipStream_t st, const BnFold &bn = BnFold())
 {
     LSN_CHECK(w && prepared, "conv2d prepare: NULL pointer");
-    LSN_CHECK(C > 0 && Co > 0 && kh > 0 && kw > 0 && kh * kw <= 64, "conv2d prepare: bad weight shape");
+    LSN_CHECK(C > 0 && Co > 0 && kh > 0 && kw > 0, "conv2d prepare: bad weight shape");
+    // (a valid convolution that this build does not serve -- the answer of conv_check, which the one-shot entries reach only
+    // behind this call)
+    if (kh * kw > 64) return fail(LSN_ERR_UNSUPPORTED, "conv2d kernel takes at most 64 taps, got %d x %d", kh, kw);
     if (prepared_bytes(kind, C, Co, kh, kw, stride, pad, dil) >= ((int64_t)1 << 31))
         return fail(LSN_ERR_UNSUPPORTED, "conv2d: weight too large for 32-bit buffer offsets");
     if (kind == 0) {

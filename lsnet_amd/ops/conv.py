@@ -818,4 +818,4 @@ class Conv2d(nn.Conv2d):
             return _GroupConvFn.apply(x, w, self.bias, self.stride[0], self.padding[0], self.dilation[0], self.groups)
         _warn_aten_fallback('Conv2d', x, f'weight {tuple(w.shape)}, stride {self.stride}, groups {self.groups}, '
                                            f'padding_mode {self.padding_mode}, input {tuple(x.shape)} {x.dtype}')
-        return F.conv2d(x, w, self.bias, self.stride, self.padding, self.dilation, self.groups)
+        return self._conv_forward(x, w, self.bias)     # (nn.Conv2d's own: F.conv2d behind the module's padding_mode)
