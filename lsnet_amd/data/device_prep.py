@@ -8,8 +8,6 @@ needed: on a GPU one `lsn_image_prep_u8` launch per image writes straight into t
 (csrc/image.hip; the upload is 1 byte per sample of the ORIGINAL image instead of 4 bytes per sample of the padded
 one), on the CPU the host library does the same arithmetic.  Both give the tensor the eager pipeline gives, bit for bit
 (tests/test_data_pipeline.py, tests/test_zz_device_prep_gpu.py)."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -51,8 +49,7 @@ def prepare_batch(images, metas, device=None):
         return batch
     from .. import _lib
     lib = _lib.load()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    f32p = ctypes.POINTER(ctypes.c_float)
+    stream = torch.cuda.current_stream(device).cuda_stream
     keep = []
     for b, (img, p) in enumerate(zip(images, plans)):
         t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
@@ -64,8 +61,7 @@ def prepare_batch(images, metas, device=None):
         inv = np.ascontiguousarray((1.0 / p['std'].astype(np.float64)).astype(np.float32))
         horizontal = p['flip'] and p['direction'] == 'horizontal'
         vertical = p['flip'] and p['direction'] == 'vertical'
-        _lib.check(lib.lsn_image_prep_u8(ctypes.c_void_p(t.data_ptr()), int(t.shape[0]), int(t.shape[1]), c, p['size'][1],
-                                         p['size'][0], int(horizontal), int(vertical), mean.ctypes.data_as(f32p),
-                                         inv.ctypes.data_as(f32p), int(p['to_rgb']), ctypes.c_float(0.0),
-                                         ctypes.c_void_p(batch[b].data_ptr()), H, W, stream))
+        _lib.check(lib.lsn_image_prep_u8(_lib.ptr(t), int(t.shape[0]), int(t.shape[1]), c, p['size'][1], p['size'][0],
+                                         int(horizontal), int(vertical), mean.ctypes.data, inv.ctypes.data, int(p['to_rgb']), 0.0,
+                                         _lib.ptr(batch[b]), H, W, stream))
     return batch

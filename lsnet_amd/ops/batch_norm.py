@@ -5,23 +5,15 @@ and keeps its BatchNorm layers in eval mode while training (`norm_eval=True`, :6
 value through one HIP kernel each way (csrc/norm.hip, lsn_bn_eval_act_*) when the layer is in eval mode and the
 tensor is CUDA / channels-last / fp32 / a supported channel count; otherwise it is the reference's sequence of
 ATen ops (training-mode batch statistics are not on the LSNet path)."""
-import ctypes
 
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from .._lib import ptr, stream
 from . import grad_sink
 
 _CL = torch.channels_last
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _BnActFn(torch.autograd.Function):
@@ -30,9 +22,8 @@ class _BnActFn(torch.autograd.Function):
     def forward(ctx, x, residual, gamma, beta, mean, var, eps, relu):
         B, C, H, W = x.shape
         y = torch.empty_like(x, memory_format=_CL)
-        _lib.check(_lib.load().lsn_bn_eval_act_forward(_p(x), _p(residual), _p(y), _p(mean), _p(var), _p(gamma),
-                                                       _p(beta), ctypes.c_float(eps), 1 if relu else 0, B * H * W, C,
-                                                       _stream()))
+        _lib.check(_lib.load().lsn_bn_eval_act_forward(ptr(x), ptr(residual), ptr(y), ptr(mean), ptr(var), ptr(gamma),
+                                                       ptr(beta), eps, 1 if relu else 0, B * H * W, C, stream()))
         ctx.save_for_backward(x, y if relu else None, gamma, mean, var)
         ctx.cfg = (eps, relu, residual is not None)
         ctx.beta_ref = beta    # backward only asks where its gradient goes (ops/grad_sink.py)
@@ -60,9 +51,8 @@ class _BnActFn(torch.autograd.Function):
         lib = _lib.load()
         ws = torch.empty(lib.lsn_bn_eval_act_workspace_bytes(B * H * W, C), device=x.device, dtype=torch.uint8) \
             if need_p else None
-        _lib.check(lib.lsn_bn_eval_act_backward(_p(dy), _p(y), _p(x), _p(mean), _p(var), _p(gamma), ctypes.c_float(eps),
-                                                1 if relu else 0, _p(dx), _p(dres), _p(dg), _p(db), _p(ws), B * H * W, C,
-                                                acc, _stream()))
+        _lib.check(lib.lsn_bn_eval_act_backward(ptr(dy), ptr(y), ptr(x), ptr(mean), ptr(var), ptr(gamma), eps, 1 if relu else 0,
+                                                ptr(dx), ptr(dres), ptr(dg), ptr(db), ptr(ws), B * H * W, C, acc, stream()))
         if acc:
             grad_sink.done(gamma)
             grad_sink.done(ctx.beta_ref)

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from .._lib import ptr, stream
 from . import grad_sink
 from .streams import side_stream
 
@@ -40,14 +41,6 @@ def _warn_aten_fallback(what, x, detail):
     import warnings
     warnings.warn(f'lsnet_amd.{what}: no HIP kernel of this library serves this call on {x.device} ({detail}); '
                   'falling back to the ATen operator', RuntimeWarning, stacklevel=3)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _pad_channels(t, c_to):
@@ -156,7 +149,7 @@ def _refresh_stale(mode):
         for key, ent, w in items:
             it = _lib.ConvWprep()
             _fill_item(it, key, ent, w)
-            _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), _stream()))
+            _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), stream()))
     else:
         arr = (_lib.ConvWprep * len(items))()
         for it, (key, ent, w) in zip(arr, items):
@@ -178,10 +171,10 @@ def _refresh_stale(mode):
             side = side_stream(torch.device('cuda', dev))       # (ONE per process and device: ops/streams.py says why)
             side.wait_event(ev)
             with torch.cuda.stream(side):
-                _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, _stream()))
+                _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, stream()))
             main.wait_stream(side)
         else:
-            _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, _stream()))
+            _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, stream()))
     for key, ent, w in items:
         _mark_fresh(ent, w)
 
@@ -213,7 +206,7 @@ def weight_image(w, kind, stride=1, pad=0, dil=1, bn=None):
            weakref.ref(bn) if bn is not None else None, shift, _bn_versions(bn) if bn is not None else None]
     it = _lib.ConvWprep()
     _fill_item(it, key, ent, w)
-    _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), _stream()))
+    _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), stream()))
     _images[key] = ent
     return img if (bn is None or kind == 1) else (img, shift)
 
@@ -275,14 +268,14 @@ def relu_gate_multi(gys, ys):
     for j, (g, y, o, sb) in enumerate(zip(gys, ys, outs, strides)):
         jobs[j].grad_y, jobs[j].y, jobs[j].grad = g.data_ptr(), y.data_ptr(), o.data_ptr()
         jobs[j].B, jobs[j].per_image, jobs[j].gy_batch_stride = y.shape[0], y.numel() // y.shape[0], sb
-    _lib.check(_lib.load().lsn_relu_gate_multi(n, jobs, _stream()))
+    _lib.check(_lib.load().lsn_relu_gate_multi(n, jobs, stream()))
     return outs
 
 
 def relu_gate(gy, y):
     """grad_y where y > 0, else 0 -- the gradient through a ReLU whose output was stored (lsn_relu_gate)."""
     g = torch.empty_like(y, memory_format=_CL)
-    _lib.check(_lib.load().lsn_relu_gate(_p(gy), _p(y), _p(g), ctypes.c_int64(y.numel()), _stream()))
+    _lib.check(_lib.load().lsn_relu_gate(ptr(gy), ptr(y), ptr(g), y.numel(), stream()))
     return g
 
 
@@ -295,10 +288,10 @@ def dgrad(g, w, in_shape, stride, pad, dil, bn=None, residual=None, gate=None, o
     if out is None:
         out = torch.empty(in_shape, device=g.device, dtype=torch.float32, memory_format=_CL)
     lv = _levels(1)
-    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = _p(g), _p(out), B, H, W
-    lv[0].residual, lv[0].gate = _p(residual), _p(gate)
-    _lib.check(_lib.load().lsn_conv2d_backward_data_prepared(1, lv, _p(weight_image(w, 1, stride, pad, dil, bn=bn)), C, Co, kh,
-                                                             kw, stride, pad, dil, _stream()))
+    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(g), ptr(out), B, H, W
+    lv[0].residual, lv[0].gate = ptr(residual), ptr(gate)
+    _lib.check(_lib.load().lsn_conv2d_backward_data_prepared(1, lv, ptr(weight_image(w, 1, stride, pad, dil, bn=bn)), C, Co, kh,
+                                                             kw, stride, pad, dil, stream()))
     return out
 
 
@@ -317,8 +310,8 @@ def wgrad_bn(x, g, w, bn, stride, pad, dil, need=(True, True, True)):
     else:
         gw, dg, db = torch.empty_like(w), torch.empty_like(gamma), torch.empty_like(beta)
     _lib.check(_lib.load().lsn_conv2d_backward_weight_bn(
-        _p(x), _p(g), _p(w), _p(gamma), _p(bn.running_mean), _p(bn.running_var), ctypes.c_float(float(bn.eps)), _p(gw),
-        _p(dg), _p(db), B, H, W, C, Co, kh, kw, stride, pad, dil, acc, _stream()))
+        ptr(x), ptr(g), ptr(w), ptr(gamma), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(gw),
+        ptr(dg), ptr(db), B, H, W, C, Co, kh, kw, stride, pad, dil, acc, stream()))
     if acc:
         grad_sink.done(w)
         grad_sink.done(gamma)
@@ -347,10 +340,11 @@ def wgrad_bn_jobs(jobs, stride, pad, dil):
         arr = (_lib.WgradBnJob * len(part))()
         for q, (x, g, w, bn) in zip(arr, part):
             assert x.shape == x0.shape and w.shape == w0.shape
-            q.x, q.g, q.w = _p(x), _p(g), _p(w)
-            q.bn_gamma, q.bn_mean, q.bn_var, q.bn_eps = _p(bn.weight), _p(bn.running_mean), _p(bn.running_var), float(bn.eps)
-            q.grad_w, q.grad_gamma, q.grad_beta = _p(grad_sink.sink(w)), _p(grad_sink.sink(bn.weight)), _p(grad_sink.sink(bn.bias))
-        _lib.check(lib.lsn_conv2d_backward_weight_bn_jobs(len(part), arr, B, H, W, C, Co, kh, kw, stride, pad, dil, 1, _stream()))
+            q.x, q.g, q.w = ptr(x), ptr(g), ptr(w)
+            q.bn_gamma, q.bn_mean, q.bn_var, q.bn_eps = ptr(bn.weight), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps)
+            q.grad_w, q.grad_gamma, q.grad_beta = ptr(grad_sink.sink(w)), ptr(grad_sink.sink(bn.weight)), \
+                ptr(grad_sink.sink(bn.bias))
+        _lib.check(lib.lsn_conv2d_backward_weight_bn_jobs(len(part), arr, B, H, W, C, Co, kh, kw, stride, pad, dil, 1, stream()))
     for _, _, w, bn in jobs:
         grad_sink.done(w)
         grad_sink.done(bn.weight)
@@ -366,9 +360,9 @@ def conv_fwd_bn(x, w, bn, stride, pad, dil, relu, residual=None):
     img, shift = weight_image(w, 0, bn=bn)
     out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
     lv = _levels(1)
-    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = _p(x), _p(out), B, H, W, _p(residual)
-    _lib.check(_lib.load().lsn_conv2d_forward_prepared(1, lv, _p(img), _p(shift), C, C, Co, kh, kw, stride, pad, dil,
-                                                       1 if relu else 0, _stream()))
+    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = ptr(x), ptr(out), B, H, W, ptr(residual)
+    _lib.check(_lib.load().lsn_conv2d_forward_prepared(1, lv, ptr(img), ptr(shift), C, C, Co, kh, kw, stride, pad, dil,
+                                                       1 if relu else 0, stream()))
     return out
 
 
@@ -386,9 +380,9 @@ class _ConvFn(torch.autograd.Function):
         w = w.contiguous(memory_format=_CL)
         out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
         lv = _levels(1)
-        lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = _p(x), _p(out), B, H, W
-        _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, _p(weight_image(w, 0)), _p(bias), C, C, Co, kh, kw, stride, pad,
-                                                   dil, 1 if relu else 0, _stream()))
+        lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(x), ptr(out), B, H, W
+        _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, ptr(weight_image(w, 0)), ptr(bias), C, C, Co, kh, kw, stride, pad,
+                                                   dil, 1 if relu else 0, stream()))
         ctx.save_for_backward(x, w, out if relu else None)
         ctx.cfg = (stride, pad, dil, relu, bias is not None)
         ctx.bias_ref = bias    # (not saved for its value: backward only asks where its gradient goes)
@@ -415,15 +409,15 @@ class _ConvFn(torch.autograd.Function):
                 w8[:Co] = w
             gx = torch.empty_like(x, memory_format=_CL)
             lv = _levels(1)
-            lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = _p(go8), _p(gx), B, H, W
-            _lib.check(lib.lsn_conv2d_backward_data_prepared(1, lv, _p(weight_image(w8, 1, stride, pad, dil)), C, Co8, kh,
-                                                             kw, stride, pad, dil, _stream()))
+            lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(go8), ptr(gx), B, H, W
+            _lib.check(lib.lsn_conv2d_backward_data_prepared(1, lv, ptr(weight_image(w8, 1, stride, pad, dil)), C, Co8, kh,
+                                                             kw, stride, pad, dil, stream()))
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             # weight gradient and the bias gradient in one pass over grad_output
             want_b = has_bias and ctx.needs_input_grad[2]
             gw, gb, acc = _param_grad_buffers(w, ctx.bias_ref if want_b else None, ctx.needs_input_grad[1], want_b)
-            _lib.check(lib.lsn_conv2d_backward_weight(_p(x), _p(go), _p(gw), _p(gb), B, H, W, C, Co, kh, kw, stride, pad,
-                                                      dil, acc, _stream()))
+            _lib.check(lib.lsn_conv2d_backward_weight(ptr(x), ptr(go), ptr(gw), ptr(gb), B, H, W, C, Co, kh, kw, stride, pad,
+                                                      dil, acc, stream()))
             gw, gb = _param_grad_results(w, ctx.bias_ref if want_b else None, gw, gb, acc, ctx.needs_input_grad[1])
         return gx, gw, gb, None, None, None, None
 
@@ -440,8 +434,8 @@ class _GroupConvFn(torch.autograd.Function):
         Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
         w = w.contiguous(memory_format=_CL)
         out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-        _lib.check(lib.lsn_grouped_conv2d_forward(_p(x), _p(w), _p(bias), _p(out), B, H, W, C, Co, kh, kw, stride, pad, dil,
-                                                  groups, 0, _stream()))
+        _lib.check(lib.lsn_grouped_conv2d_forward(ptr(x), ptr(w), ptr(bias), ptr(out), B, H, W, C, Co, kh, kw, stride, pad, dil,
+                                                  groups, 0, stream()))
         ctx.save_for_backward(x, w)
         ctx.cfg = (stride, pad, dil, groups, bias is not None)
         return out
@@ -458,13 +452,13 @@ class _GroupConvFn(torch.autograd.Function):
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x, memory_format=_CL)
-            _lib.check(lib.lsn_grouped_conv2d_backward_data(_p(go), _p(w), _p(gx), B, H, W, C, Co, kh, kw, stride, pad, dil,
-                                                            groups, _stream()))
+            _lib.check(lib.lsn_grouped_conv2d_backward_data(ptr(go), ptr(w), ptr(gx), B, H, W, C, Co, kh, kw, stride, pad, dil,
+                                                            groups, stream()))
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             gw = torch.empty_like(w)
             gb = torch.empty(Co, device=x.device, dtype=torch.float32) if has_bias and ctx.needs_input_grad[2] else None
-            _lib.check(lib.lsn_grouped_conv2d_backward_weight(_p(x), _p(go), _p(gw), _p(gb), B, H, W, C, Co, kh, kw, stride,
-                                                              pad, dil, groups, 0, _stream()))
+            _lib.check(lib.lsn_grouped_conv2d_backward_weight(ptr(x), ptr(go), ptr(gw), ptr(gb), B, H, W, C, Co, kh, kw, stride,
+                                                              pad, dil, groups, 0, stream()))
             if not ctx.needs_input_grad[1]:
                 gw = None
         return gx, gw, gb, None, None, None, None
@@ -497,12 +491,12 @@ def conv_multi_fwd(xs, w, bias, pad, dil, relu, residuals=None):
         out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
         outs.append(out)
         L = levels[i]
-        L.x, L.out, L.B, L.H, L.W = _p(x), _p(out), B, H, W
+        L.x, L.out, L.B, L.H, L.W = ptr(x), ptr(out), B, H, W
         if residuals is not None:
             assert residuals[i].shape == out.shape and residuals[i].is_contiguous(memory_format=_CL)
-            L.residual = _p(residuals[i])
-    _lib.check(_lib.load().lsn_conv2d_forward_prepared(n, levels, _p(weight_image(w, 0)), _p(bias), C, C, Co, kh, kw, 1, pad, dil,
-                                                       1 if relu else 0, _stream()))
+            L.residual = ptr(residuals[i])
+    _lib.check(_lib.load().lsn_conv2d_forward_prepared(n, levels, ptr(weight_image(w, 0)), ptr(bias), C, C, Co, kh, kw, 1, pad, dil,
+                                                       1 if relu else 0, stream()))
     return outs
 
 
@@ -524,11 +518,11 @@ def conv_multi_dgrad(gos, w, xs, pad, dil, accumulate_into=None):
         gx = accumulate_into[i] if accumulate_into is not None else torch.empty_like(x, memory_format=_CL)
         gxs.append(gx)
         L = levels[i]
-        L.x, L.out, L.B, L.H, L.W = _p(gos8[i]), _p(gx), x.shape[0], x.shape[2], x.shape[3]
+        L.x, L.out, L.B, L.H, L.W = ptr(gos8[i]), ptr(gx), x.shape[0], x.shape[2], x.shape[3]
         if accumulate_into is not None:
-            L.residual = _p(gx)
-    _lib.check(_lib.load().lsn_conv2d_backward_data_prepared(n, levels, _p(weight_image(w8, 1, 1, pad, dil)), C, Co8, kh, kw, 1,
-                                                             pad, dil, _stream()))
+            L.residual = ptr(gx)
+    _lib.check(_lib.load().lsn_conv2d_backward_data_prepared(n, levels, ptr(weight_image(w8, 1, 1, pad, dil)), C, Co8, kh, kw, 1,
+                                                             pad, dil, stream()))
     return gxs
 
 
@@ -540,10 +534,10 @@ def conv_multi_wgrad(xs, gos, w, bias, pad, dil, want_w=True, want_b=True):
     levels = (_lib.ConvLevel * n)()
     for i, x in enumerate(xs):
         L = levels[i]
-        L.x, L.grad_out, L.B, L.H, L.W = _p(x), _p(gos[i]), x.shape[0], x.shape[2], x.shape[3]
+        L.x, L.grad_out, L.B, L.H, L.W = ptr(x), ptr(gos[i]), x.shape[0], x.shape[2], x.shape[3]
     want_b = want_b and bias is not None
     gw, gb, acc = _param_grad_buffers(w, bias if want_b else None, want_w, want_b)
-    _lib.check(_lib.load().lsn_conv2d_backward_weight_multi(n, levels, _p(gw), _p(gb), C, Co, kh, kw, 1, pad, dil, acc, _stream()))
+    _lib.check(_lib.load().lsn_conv2d_backward_weight_multi(n, levels, ptr(gw), ptr(gb), C, Co, kh, kw, 1, pad, dil, acc, stream()))
     return _param_grad_results(w, bias if want_b else None, gw, gb, acc, want_w)
 
 
@@ -644,8 +638,8 @@ def _stem_forward(x, weight, bias, stride, pad, relu):
     w4[:, :C] = weight
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-    _lib.check(lib.lsn_conv2d_forward_pitched(_p(xp), _p(w4), _p(bias), _p(out), None, B, H + 2 * pad, W + 2 * pad,
-                                              kw * C4, C4, Co, kh, 1, stride, 0, 1, 1 if relu else 0, _stream()))
+    _lib.check(lib.lsn_conv2d_forward_pitched(ptr(xp), ptr(w4), ptr(bias), ptr(out), None, B, H + 2 * pad, W + 2 * pad,
+                                              kw * C4, C4, Co, kh, 1, stride, 0, 1, 1 if relu else 0, stream()))
     return out
 
 
@@ -718,9 +712,9 @@ def conv_bn_act_frozen(conv, bn, x, relu=True, residual=None):
     lib = _lib.load()
     out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
     lv = _levels(1)
-    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = _p(x), _p(out), B, H, W, _p(residual)
-    _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, _p(weight_image(w, 0)), _p(shift), C, C, Co, kh, kw, stride, pad,
-                                               dil, 1 if relu else 0, _stream()))
+    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = ptr(x), ptr(out), B, H, W, ptr(residual)
+    _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, ptr(weight_image(w, 0)), ptr(shift), C, C, Co, kh, kw, stride, pad,
+                                               dil, 1 if relu else 0, stream()))
     return out
 
 

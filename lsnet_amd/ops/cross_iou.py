@@ -3,24 +3,16 @@ elementwise launches of the torch formulation (models/losses/cross_iou_loss.py) 
 (lsn_cross_iou_bbox_forward / _backward and the whole-stage variant), the polygon (instance segmentation) and the
 keypoint (pose) tasks (lsn_cross_iou_rows_forward / _backward).  On by default for device tensors (verified on the MI355X against the torch
 formulation and the reference fixture: tests/test_zz_fused_ciou_gpu.py); `LSNET_FUSED_CIOU=0` keeps the torch formulation."""
-import ctypes
 import os
 
 import torch
 
 from .. import _lib
+from .._lib import ptr, stream
 
 
 def enabled():
     return os.environ.get('LSNET_FUSED_CIOU', '1') != '0'
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _CrossIouBbox(torch.autograd.Function):
@@ -32,9 +24,8 @@ class _CrossIouBbox(torch.autograd.Function):
         anchor, bbox_gt = anchor.contiguous(), bbox_gt.contiguous()
         weight = None if weight is None else weight.contiguous()
         loss = torch.empty(pred.shape[0], dtype=torch.float32, device=pred.device)
-        _lib.check(_lib.load().lsn_cross_iou_bbox_forward(_p(pred), _p(target), _p(active), _p(anchor), _p(bbox_gt), _p(weight),
-                                                          ctypes.c_int64(pred.shape[0]), ctypes.c_float(alpha),
-                                                          ctypes.c_float(eps), _p(loss), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_bbox_forward(ptr(pred), ptr(target), ptr(active), ptr(anchor), ptr(bbox_gt),
+                                                          ptr(weight), pred.shape[0], alpha, eps, ptr(loss), stream()))
         ctx.save_for_backward(pred, target, active, anchor, bbox_gt, *([weight] if weight is not None else []))
         ctx.cfg = (alpha, eps, weight is not None)
         return loss
@@ -46,9 +37,9 @@ class _CrossIouBbox(torch.autograd.Function):
         pred, target, active, anchor, bbox_gt, *rest = ctx.saved_tensors
         weight = rest[0] if has_w else None
         grad = torch.empty_like(pred)
-        _lib.check(_lib.load().lsn_cross_iou_bbox_backward(_p(pred), _p(target), _p(active), _p(anchor), _p(bbox_gt), _p(weight),
-                                                           _p(grad_rows.contiguous()), ctypes.c_int64(pred.shape[0]),
-                                                           ctypes.c_float(alpha), ctypes.c_float(eps), _p(grad), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_bbox_backward(ptr(pred), ptr(target), ptr(active), ptr(anchor), ptr(bbox_gt),
+                                                           ptr(weight), ptr(grad_rows.contiguous()), pred.shape[0], alpha, eps,
+                                                           ptr(grad), stream()))
         return grad, None, None, None, None, None, None, None
 
 
@@ -87,9 +78,8 @@ class _CrossIouRows(torch.autograd.Function):
         active = active.to(torch.uint8).contiguous()
         n, m = pred.shape
         loss = torch.empty(n, dtype=torch.float32, device=pred.device)
-        _lib.check(_lib.load().lsn_cross_iou_rows_forward(kind, _p(pred), _p(target), _p(active), _p(anchor), _p(bbox_gt), _p(vs),
-                                                          _p(weight), ctypes.c_int64(n), m, sub, ctypes.c_float(alpha),
-                                                          ctypes.c_float(eps), _p(loss), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_rows_forward(kind, ptr(pred), ptr(target), ptr(active), ptr(anchor), ptr(bbox_gt),
+                                                          ptr(vs), ptr(weight), n, m, sub, alpha, eps, ptr(loss), stream()))
         ctx.save_for_backward(pred, target, active, anchor, bbox_gt, vs, weight)   # (None entries are allowed)
         ctx.cfg = (kind, sub, alpha, eps)
         return loss
@@ -101,9 +91,9 @@ class _CrossIouRows(torch.autograd.Function):
         pred, target, active, anchor, bbox_gt, vs, weight = ctx.saved_tensors
         n, m = pred.shape
         grad = torch.empty_like(pred)
-        _lib.check(_lib.load().lsn_cross_iou_rows_backward(kind, _p(pred), _p(target), _p(active), _p(anchor), _p(bbox_gt), _p(vs),
-                                                           _p(weight), _p(grad_rows.contiguous()), ctypes.c_int64(n), m, sub,
-                                                           ctypes.c_float(alpha), ctypes.c_float(eps), _p(grad), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_rows_backward(kind, ptr(pred), ptr(target), ptr(active), ptr(anchor), ptr(bbox_gt),
+                                                           ptr(vs), ptr(weight), ptr(grad_rows.contiguous()), n, m, sub, alpha, eps,
+                                                           ptr(grad), stream()))
         return (grad,) + (None,) * 10
 
 
@@ -127,9 +117,8 @@ class _CrossIouBboxStage(torch.autograd.Function):
         raw, gt_pts, anchor3 = raw.contiguous(), gt_pts.contiguous(), anchor3.contiguous()
         bbox_gt, weight = bbox_gt.contiguous(), weight.contiguous()
         loss = torch.empty(raw.shape[0], dtype=torch.float32, device=raw.device)
-        _lib.check(_lib.load().lsn_cross_iou_bbox_stage_forward(_p(raw), _p(gt_pts), _p(anchor3), _p(bbox_gt), _p(weight),
-                                                                ctypes.c_int64(raw.shape[0]), ctypes.c_float(base),
-                                                                ctypes.c_float(alpha), ctypes.c_float(eps), _p(loss), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_bbox_stage_forward(ptr(raw), ptr(gt_pts), ptr(anchor3), ptr(bbox_gt), ptr(weight),
+                                                                raw.shape[0], base, alpha, eps, ptr(loss), stream()))
         ctx.save_for_backward(raw, gt_pts, anchor3, bbox_gt, weight)
         ctx.cfg = (base, alpha, eps)
         return loss
@@ -140,10 +129,9 @@ class _CrossIouBboxStage(torch.autograd.Function):
         base, alpha, eps = ctx.cfg
         raw, gt_pts, anchor3, bbox_gt, weight = ctx.saved_tensors
         grad = torch.empty_like(raw)
-        _lib.check(_lib.load().lsn_cross_iou_bbox_stage_backward(_p(raw), _p(gt_pts), _p(anchor3), _p(bbox_gt), _p(weight),
-                                                                 _p(grad_rows.contiguous()), ctypes.c_int64(raw.shape[0]),
-                                                                 ctypes.c_float(base), ctypes.c_float(alpha), ctypes.c_float(eps),
-                                                                 _p(grad), _stream()))
+        _lib.check(_lib.load().lsn_cross_iou_bbox_stage_backward(ptr(raw), ptr(gt_pts), ptr(anchor3), ptr(bbox_gt), ptr(weight),
+                                                                 ptr(grad_rows.contiguous()), raw.shape[0], base, alpha, eps,
+                                                                 ptr(grad), stream()))
         return grad, None, None, None, None, None, None, None
 
 

@@ -4,19 +4,13 @@ import ctypes
 import torch
 
 from .. import _lib
+from .._lib import ptr, stream
+from .._lib import ptr as _ptr, stream as _stream  # noqa: F401  (the names tests/test_ops_gpu.py imports from here)
 from .backend import register_backend
 
 _CL = torch.channels_last
 # LSNET_CACHE_DCN_IMAGES=0: the deformable layers build their weight images inside every call, as until round 5 (A/B switch)
 CACHE_DCN_IMAGES = __import__('os').environ.get('LSNET_CACHE_DCN_IMAGES', '1') != '0'
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _f32(t, what):
@@ -93,10 +87,10 @@ class HipBackend:
         for i, x in enumerate(xs):
             B, C, H, W = x.shape
             L = levels[i]
-            L.x = _ptr(x)
-            L.y = _ptr(ys[i]) if ys is not None else None
-            L.dy = _ptr(dys[i]) if dys is not None else None
-            L.dx = _ptr(dxs[i]) if dxs is not None else None
+            L.x = ptr(x)
+            L.y = ptr(ys[i]) if ys is not None else None
+            L.dy = ptr(dys[i]) if dys is not None else None
+            L.dx = ptr(dxs[i]) if dxs is not None else None
             L.B, L.HW = B, H * W
         return levels
 
@@ -125,8 +119,8 @@ class HipBackend:
         mean_rstd = torch.empty(images, groups, 2, device=xs[0].device, dtype=torch.float32)
         ws = torch.empty(lib.lsn_group_norm_workspace_bytes(n, levels, C, groups), device=xs[0].device,
                          dtype=torch.uint8)
-        _lib.check(lib.lsn_group_norm_forward(n, levels, C, groups, _ptr(gamma), _ptr(beta), ctypes.c_float(eps),
-                                              1 if relu else 0, _ptr(mean_rstd), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_group_norm_forward(n, levels, C, groups, ptr(gamma), ptr(beta), eps, 1 if relu else 0,
+                                              ptr(mean_rstd), ptr(ws), stream()))
         if cat_px:
             return flat.unsqueeze(2).permute(0, 3, 1, 2), mean_rstd      # (B, C, N_all, 1), channels-last memory
         return ys, mean_rstd
@@ -162,9 +156,8 @@ class HipBackend:
             db = torch.empty_like(beta) if need_params else None
         ws = torch.empty(lib.lsn_group_norm_workspace_bytes(n, levels, C, groups), device=xs[0].device,
                          dtype=torch.uint8)
-        _lib.check(lib.lsn_group_norm_backward(n, levels, C, groups, _ptr(gamma), _ptr(beta), 1 if relu else 0,
-                                               _ptr(mean_rstd), _ptr(dg), _ptr(db), _ptr(ws), 1 if sinks else 0,
-                                               _stream()))
+        _lib.check(lib.lsn_group_norm_backward(n, levels, C, groups, ptr(gamma), ptr(beta), 1 if relu else 0,
+                                               ptr(mean_rstd), ptr(dg), ptr(db), ptr(ws), 1 if sinks else 0, stream()))
         return dxs, dg, db
 
     # ------------------------------------------------------------------ deformable conv family
@@ -194,7 +187,7 @@ class HipBackend:
     def _mask_view_ptr(om, cfg, kk):
         """Fused DCNv2 pack: `om` (B, 3*dg*K, H, W) holds offsets in its first 2*dg*K channels and the
         mask logits in the rest; the mask pointer is the same buffer advanced by 2*dg*K channels."""
-        return ctypes.c_void_p(om.data_ptr() + 2 * cfg['dg'] * kk * om.stride(1) * om.element_size())
+        return om.data_ptr() + 2 * cfg['dg'] * kk * om.stride(1) * om.element_size()
 
     @staticmethod
     def _cached_image(w, weight, cfg, kind, nhwc):
@@ -240,7 +233,7 @@ class HipBackend:
                                   memory_format=_CL if nhwc else torch.contiguous_format)
             outs.append(out)
             L = levels[i]
-            L.input, L.offset, L.mask, L.output = _ptr(xs[i]), _ptr(offs[i]), _ptr(msks[i]), _ptr(out)
+            L.input, L.offset, L.mask, L.output = ptr(xs[i]), ptr(offs[i]), ptr(msks[i]), ptr(out)
             L.off_st = _strides(offs[i])
             if cfg.get('fused_om'):
                 L.mask, L.mask_st = self._mask_view_ptr(offs[i], cfg, w.shape[2] * w.shape[3]), _strides(offs[i])
@@ -265,9 +258,8 @@ class HipBackend:
                 wide = None
                 outs = [torch.empty(tuple(o.shape), device=o.device, dtype=torch.float32, memory_format=_CL) for o in outs]
                 for i in range(n):
-                    levels[i].output = _ptr(outs[i])
-        _lib.check(lib.lsn_dcn_forward(ctypes.byref(shape), n, levels, _ptr(w), _ptr(b), 1 if nhwc else 0,
-                                       _stream()))
+                    levels[i].output = ptr(outs[i])
+        _lib.check(lib.lsn_dcn_forward(ctypes.byref(shape), n, levels, ptr(w), ptr(b), 1 if nhwc else 0, stream()))
         if g > 1:
             return wide if wide is not None else [torch.cat(outs[j:j + g], dim=1) for j in range(0, n, g)]
         return outs
@@ -326,8 +318,8 @@ class HipBackend:
             go, gx, goff, gmsk = gos[i], gx_bufs[i], goffs[i], gmsks[i]
             Ho, Wo = go.shape[2], go.shape[3]
             L = levels[i]
-            L.input, L.offset, L.mask = _ptr(xs[i]), _ptr(offs[i]), _ptr(msks[i])
-            L.grad_output, L.grad_input, L.grad_offset, L.grad_mask = _ptr(go), _ptr(gx), _ptr(goff), _ptr(gmsk)
+            L.input, L.offset, L.mask = ptr(xs[i]), ptr(offs[i]), ptr(msks[i])
+            L.grad_output, L.grad_input, L.grad_offset, L.grad_mask = ptr(go), ptr(gx), ptr(goff), ptr(gmsk)
             L.off_st = _strides(offs[i])
             if cfg.get('fused_om'):
                 kk = w.shape[2] * w.shape[3]
@@ -365,9 +357,9 @@ class HipBackend:
                 shape.out_pitch = 0
                 gos = [g.contiguous(memory_format=_CL) for g in gos]
                 for i in range(n):
-                    levels[i].grad_output = _ptr(gos[i])
-        _lib.check(lib.lsn_dcn_backward(ctypes.byref(shape), n, levels, _ptr(w), _ptr(gw), _ptr(gb),
-                                        1 if nhwc else 0, _stream()))
+                    levels[i].grad_output = ptr(gos[i])
+        _lib.check(lib.lsn_dcn_backward(ctypes.byref(shape), n, levels, ptr(w), ptr(gw), ptr(gb),
+                                        1 if nhwc else 0, stream()))
 
     # ------------------------------------------------------------------ sigmoid focal loss
     def focal_forward(self, logits, targets, gamma, alpha):
@@ -378,8 +370,8 @@ class HipBackend:
             raise TypeError('targets must be int64')
         out = torch.empty_like(logits)
         N, C = logits.shape
-        _lib.check(lib.lsn_sigmoid_focal_loss_forward(_ptr(logits), _ptr(targets), _ptr(out), N, C,
-                                                      ctypes.c_float(gamma), ctypes.c_float(alpha), _stream()))
+        _lib.check(lib.lsn_sigmoid_focal_loss_forward(ptr(logits), ptr(targets), ptr(out), N, C, gamma, alpha,
+                                                      stream()))
         return out
 
     def focal_backward(self, logits, targets, d_losses, gamma, alpha):
@@ -388,9 +380,8 @@ class HipBackend:
         d_losses = d_losses.contiguous()
         out = torch.empty_like(logits)
         N, C = logits.shape
-        _lib.check(lib.lsn_sigmoid_focal_loss_backward(_ptr(logits), _ptr(targets.contiguous()), _ptr(d_losses),
-                                                       _ptr(out), N, C, ctypes.c_float(gamma),
-                                                       ctypes.c_float(alpha), _stream()))
+        _lib.check(lib.lsn_sigmoid_focal_loss_backward(ptr(logits), ptr(targets.contiguous()), ptr(d_losses),
+                                                       ptr(out), N, C, gamma, alpha, stream()))
         return out
 
     def focal_sum(self, logits, targets, weight, gamma, alpha):
@@ -399,8 +390,8 @@ class HipBackend:
         out = torch.empty((), device=logits.device, dtype=torch.float32)
         N, C = logits.shape
         w = None if weight is None else _f32(weight, 'weight').contiguous()
-        _lib.check(lib.lsn_sigmoid_focal_loss_sum(_ptr(logits), _ptr(targets.contiguous()), _ptr(w), _ptr(out), N,
-                                                  C, ctypes.c_float(gamma), ctypes.c_float(alpha), _stream()))
+        _lib.check(lib.lsn_sigmoid_focal_loss_sum(ptr(logits), ptr(targets.contiguous()), ptr(w), ptr(out), N,
+                                                  C, gamma, alpha, stream()))
         return out
 
     def focal_backward_weighted(self, logits, targets, weight, scale, gamma, alpha):
@@ -411,8 +402,7 @@ class HipBackend:
         w = None if weight is None else weight.contiguous()
         scale = scale.to(torch.float32).contiguous()
         _lib.check(lib.lsn_sigmoid_focal_loss_backward_weighted(
-            _ptr(logits), _ptr(targets.contiguous()), _ptr(w), _ptr(scale), _ptr(out), N, C,
-            ctypes.c_float(gamma), ctypes.c_float(alpha), _stream()))
+            ptr(logits), ptr(targets.contiguous()), ptr(w), ptr(scale), ptr(out), N, C, gamma, alpha, stream()))
         return out
 
     # ------------------------------------------------------------------ per-level loss sums (LSHead's concatenated rows)
@@ -434,9 +424,8 @@ class HipBackend:
         N, C = logits.shape
         assert N == B * nall and targets.numel() == N
         out = torch.empty(len(num_level), device=logits.device, dtype=torch.float32)
-        _lib.check(lib.lsn_sigmoid_focal_loss_level_sums(_ptr(logits), _ptr(targets), _ptr(weight), _ptr(out), B, nall, C,
-                                                         len(num_level), starts, ctypes.c_float(gamma), ctypes.c_float(alpha),
-                                                         _stream()))
+        _lib.check(lib.lsn_sigmoid_focal_loss_level_sums(ptr(logits), ptr(targets), ptr(weight), ptr(out), B, nall, C,
+                                                         len(num_level), starts, gamma, alpha, stream()))
         return out
 
     def focal_backward_levels(self, logits, targets, weight, scales, B, num_level, gamma, alpha):
@@ -446,9 +435,8 @@ class HipBackend:
         out = torch.empty_like(logits)
         scales = scales.to(torch.float32).contiguous()
         assert scales.numel() == len(num_level)
-        _lib.check(lib.lsn_sigmoid_focal_loss_backward_levels(_ptr(logits), _ptr(targets), _ptr(weight), _ptr(scales), _ptr(out),
-                                                              B, nall, C, len(num_level), starts, ctypes.c_float(gamma),
-                                                              ctypes.c_float(alpha), _stream()))
+        _lib.check(lib.lsn_sigmoid_focal_loss_backward_levels(ptr(logits), ptr(targets), ptr(weight), ptr(scales), ptr(out),
+                                                              B, nall, C, len(num_level), starts, gamma, alpha, stream()))
         return out
 
     def level_sums(self, rows, B, num_level):
@@ -456,7 +444,7 @@ class HipBackend:
         starts, nall = self._level_starts(num_level)
         assert rows.is_contiguous() and rows.numel() == B * nall and rows.dtype == torch.float32
         out = torch.empty(len(num_level), device=rows.device, dtype=torch.float32)
-        _lib.check(lib.lsn_level_sums(_ptr(rows), _ptr(out), B, nall, len(num_level), starts, _stream()))
+        _lib.check(lib.lsn_level_sums(ptr(rows), ptr(out), B, nall, len(num_level), starts, stream()))
         return out
 
     def level_expand(self, g, B, num_level):
@@ -464,7 +452,7 @@ class HipBackend:
         starts, nall = self._level_starts(num_level)
         g = g.to(torch.float32).contiguous()
         out = torch.empty(B * nall, device=g.device, dtype=torch.float32)
-        _lib.check(lib.lsn_level_expand(_ptr(g), _ptr(out), B, nall, len(num_level), starts, _stream()))
+        _lib.check(lib.lsn_level_expand(ptr(g), ptr(out), B, nall, len(num_level), starts, stream()))
         return out
 
     # ------------------------------------------------------------------ NMS
@@ -479,8 +467,7 @@ class HipBackend:
         keep = torch.empty(n, dtype=torch.int64, device=dets.device)
         num = torch.zeros(1, dtype=torch.int64, device=dets.device)
         ws = torch.empty(int(lib.lsn_nms_workspace_bytes(n)), dtype=torch.uint8, device=dets.device)
-        _lib.check(lib.lsn_nms(_ptr(dets), _ptr(order), n, ctypes.c_float(iou_thr), _ptr(keep), _ptr(num),
-                               _ptr(ws), _stream()))
+        _lib.check(lib.lsn_nms(ptr(dets), ptr(order), n, iou_thr, ptr(keep), ptr(num), ptr(ws), stream()))
         return keep[:int(num.item())]
 
     # ------------------------------------------------------------------ detection decode
@@ -517,7 +504,7 @@ class HipBackend:
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         _lib.check(lib.lsn_decode_batch(B, len(levels), arr, C, hw, sf, int(num_vectors), int(kind), int(nms_pre), score_thr,
                                         iou_thr, int(bool(class_agnostic)), int(max_per_img), int(cand_cap), dets.data_ptr(),
-                                        vecs.data_ptr(), labels.data_ptr(), counts.data_ptr(), ws.data_ptr(), _stream()))
+                                        vecs.data_ptr(), labels.data_ptr(), counts.data_ptr(), ws.data_ptr(), stream()))
         return dets, vecs, labels, counts
 
     # ------------------------------------------------------------------ k nearest per column (assigners)
@@ -534,8 +521,8 @@ class HipBackend:
         idx = torch.empty((nseg * k, G), dtype=torch.int64, device=x.device)
         starts = (ctypes.c_int * nseg)(*[int(v) for v in seg_start])
         lens = (ctypes.c_int * nseg)(*[int(v) for v in seg_len])
-        _lib.check(lib.lsn_topk_columns(_ptr(x), P, G, x.stride(0), nseg, starts, lens, int(k), 1 if largest else 0,
-                                        _ptr(vals), _ptr(idx), _stream()))
+        _lib.check(lib.lsn_topk_columns(ptr(x), P, G, x.stride(0), nseg, starts, lens, int(k), 1 if largest else 0,
+                                        ptr(vals), ptr(idx), stream()))
         return vals, idx
 
     # ------------------------------------------------------------------ target assignment
@@ -570,8 +557,8 @@ class HipBackend:
         else:
             gt_inds, labels, ws = out
             assert ws.numel() >= nbytes and gt_inds.numel() == B * P and gt_inds.is_contiguous()
-        _lib.check(lib.lsn_centroid_assign_batch(_ptr(points), P, _ptr(gts), _ptr(cen), B, offs, ctypes.c_float(scale),
-                                                 int(pos_num), _ptr(lab), _ptr(gt_inds), _ptr(labels), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_centroid_assign_batch(ptr(points), P, ptr(gts), ptr(cen), B, offs, scale, int(pos_num),
+                                                 ptr(lab), ptr(gt_inds), ptr(labels), ptr(ws), stream()))
         return gt_inds, labels
 
     def centroid_assign(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, out=None):
@@ -606,8 +593,8 @@ class HipBackend:
         else:
             gt_inds, overlaps, labels, ws = out
             assert ws.numel() >= nbytes and gt_inds.numel() == B * N and gt_inds.is_contiguous() and overlaps.is_contiguous()
-        _lib.check(lib.lsn_atss_assign_batch(_ptr(bboxes), bboxes.stride(1), N, nlev, lens, _ptr(gts), B, offs, int(topk),
-                                             _ptr(lab), _ptr(gt_inds), _ptr(overlaps), _ptr(labels), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_atss_assign_batch(ptr(bboxes), bboxes.stride(1), N, nlev, lens, ptr(gts), B, offs, int(topk),
+                                             ptr(lab), ptr(gt_inds), ptr(overlaps), ptr(labels), ptr(ws), stream()))
         return gt_inds, overlaps, labels
 
     def atss_assign(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, out=None):
@@ -626,7 +613,7 @@ class HipBackend:
             raise TypeError(f'gt_inds must be int64, got {gt_inds.dtype}')
         P, D = gt_inds.numel(), table.shape[1]
         out = torch.empty((P, D), dtype=torch.float32, device=table.device)
-        _lib.check(lib.lsn_dense_targets(_ptr(gt_inds), P, _ptr(table), D, _ptr(out), _stream()))
+        _lib.check(lib.lsn_dense_targets(ptr(gt_inds), P, ptr(table), D, ptr(out), stream()))
         return out
 
     # ------------------------------------------------------------------ corner-point verification (csrc/cpv.hip)
@@ -664,8 +651,8 @@ class HipBackend:
             assert ws.numel() >= nbytes and hm.numel() == B * 2 * P and off.numel() == B * 4 * P and npos.numel() == B * 2
             assert hm.is_contiguous() and off.is_contiguous() and npos.is_contiguous() and npos.dtype == torch.int32
             _f32(hm, 'hm'), _f32(off, 'off')
-        _lib.check(lib.lsn_corner_targets_batch(_ptr(points), P, _ptr(valid), _ptr(gts), B, offs, int(bool(gaussian_bump)),
-                                                float(gaussian_iou), _ptr(hm), _ptr(off), _ptr(npos), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_corner_targets_batch(ptr(points), P, ptr(valid), ptr(gts), B, offs, int(bool(gaussian_bump)),
+                                                float(gaussian_iou), ptr(hm), ptr(off), ptr(npos), ptr(ws), stream()))
         return hm, off, npos
 
     def _corner_args(self, scores, offsets, hm, off, valid, npos, grads=None):
@@ -707,8 +694,8 @@ class HipBackend:
         else:
             heat, offl, ws = out
             assert ws.numel() * ws.element_size() >= nbytes and heat.numel() == L and offl.numel() == L
-        _lib.check(lib.lsn_corner_loss_forward(B, P, L, arr, _ptr(hm), _ptr(off), _ptr(valid), _ptr(npos), alpha, gamma, beta,
-                                               _ptr(heat), _ptr(offl), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_corner_loss_forward(B, P, L, arr, ptr(hm), ptr(off), ptr(valid), ptr(npos), alpha, gamma, beta,
+                                               ptr(heat), ptr(offl), ptr(ws), stream()))
         return heat, offl
 
     def corner_loss_backward(self, scores, offsets, hm, off, valid, npos, alpha, gamma, beta, g_heat, g_off, out=None):
@@ -719,8 +706,8 @@ class HipBackend:
         arr, B, P, valid = self._corner_args(scores, offsets, hm, off, valid, npos, grads)
         g_heat, g_off = _f32(g_heat, 'g_heat').contiguous(), _f32(g_off, 'g_off').contiguous()
         assert g_heat.numel() == len(scores) and g_off.numel() == len(scores)
-        _lib.check(lib.lsn_corner_loss_backward(B, P, len(scores), arr, _ptr(hm), _ptr(off), _ptr(valid), _ptr(npos), alpha,
-                                                gamma, beta, _ptr(g_heat), _ptr(g_off), _stream()))
+        _lib.check(lib.lsn_corner_loss_backward(B, P, len(scores), arr, ptr(hm), ptr(off), ptr(valid), ptr(npos), alpha,
+                                                gamma, beta, ptr(g_heat), ptr(g_off), stream()))
         return grads
 
     @staticmethod
@@ -760,8 +747,8 @@ class HipBackend:
         else:
             loss, stats, ws = out
             assert ws.numel() * ws.element_size() >= nbytes and loss.numel() == 1 and stats.numel() == 4
-        _lib.check(lib.lsn_sep_focal_forward(B, C, len(logits), arr, _ptr(target), _ptr(weight), target.shape[2], target.shape[3],
-                                             gamma, alpha, _ptr(loss), _ptr(stats), _ptr(ws), _stream()))
+        _lib.check(lib.lsn_sep_focal_forward(B, C, len(logits), arr, ptr(target), ptr(weight), target.shape[2], target.shape[3],
+                                             gamma, alpha, ptr(loss), ptr(stats), ptr(ws), stream()))
         return loss, stats
 
     def sep_focal_backward(self, logits, target, weight, gamma, alpha, stats, g, out=None):
@@ -771,8 +758,8 @@ class HipBackend:
         grads = out if out is not None else [torch.empty_like(x) for x in logits]
         arr, B, C, target, weight = self._sem_args(logits, target, weight, grads)
         g = _f32(g, 'g').reshape(1).contiguous()
-        _lib.check(lib.lsn_sep_focal_backward(B, C, len(logits), arr, _ptr(target), _ptr(weight), target.shape[2],
-                                              target.shape[3], gamma, alpha, _ptr(stats), _ptr(g), _stream()))
+        _lib.check(lib.lsn_sep_focal_backward(B, C, len(logits), arr, ptr(target), ptr(weight), target.shape[2],
+                                              target.shape[3], gamma, alpha, ptr(stats), ptr(g), stream()))
         return grads
 
     # ------------------------------------------------------------------ pooling family (csrc/pool.hip), channels-last
@@ -783,7 +770,7 @@ class HipBackend:
         p = pool_pitch(_f32(t, what))
         if p is None:
             raise ValueError(f'{what}: {tuple(t.shape)} with strides {t.stride()} is not (a channel slice of) a channels-last tensor')
-        return _ptr(t), p
+        return ptr(t), p
 
     @staticmethod
     def _pool_new(like, shape):
@@ -803,7 +790,7 @@ class HipBackend:
         y = self._pool_new(x, (B, C, max(Ho, 1), max(Wo, 1))) if out is None else out
         slot = torch.empty((B, max(Ho, 1), max(Wo, 1), C), device=x.device, dtype=torch.uint8) if want_slot else None
         (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
-        _lib.check(lib.lsn_max_pool2d_forward(xp, xpitch, yp, ypitch, _ptr(slot), B, H, W, C, kh, kw, stride, pad, _stream()))
+        _lib.check(lib.lsn_max_pool2d_forward(xp, xpitch, yp, ypitch, ptr(slot), B, H, W, C, kh, kw, stride, pad, stream()))
         return y, slot
 
     def max_pool2d_backward(self, grad_y, slot, x_shape, kernel, stride, pad, out=None):
@@ -811,8 +798,8 @@ class HipBackend:
         B, C, H, W = x_shape
         gx = self._pool_new(grad_y, x_shape) if out is None else out
         (gp, gpitch), (xp, xpitch) = self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
-        _lib.check(lib.lsn_max_pool2d_backward(gp, gpitch, _ptr(slot), xp, xpitch, B, H, W, C, kernel[0], kernel[1], stride, pad,
-                                               _stream()))
+        _lib.check(lib.lsn_max_pool2d_backward(gp, gpitch, ptr(slot), xp, xpitch, B, H, W, C, kernel[0], kernel[1], stride,
+                                               pad, stream()))
         return gx
 
     def avg_pool2d_forward(self, x, kernel, stride, pad, ceil_mode, count_include_pad, out=None):
@@ -823,7 +810,7 @@ class HipBackend:
         y = self._pool_new(x, (B, C, max(Ho, 1), max(Wo, 1))) if out is None else out
         (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
         _lib.check(lib.lsn_avg_pool2d_forward(xp, xpitch, yp, ypitch, B, H, W, C, kh, kw, stride, pad, 1 if ceil_mode else 0,
-                                              1 if count_include_pad else 0, _stream()))
+                                              1 if count_include_pad else 0, stream()))
         return y
 
     def avg_pool2d_backward(self, grad_y, x_shape, kernel, stride, pad, ceil_mode, count_include_pad, out=None):
@@ -832,7 +819,7 @@ class HipBackend:
         gx = self._pool_new(grad_y, x_shape) if out is None else out
         (gp, gpitch), (xp, xpitch) = self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
         _lib.check(lib.lsn_avg_pool2d_backward(gp, gpitch, xp, xpitch, B, H, W, C, kernel[0], kernel[1], stride, pad,
-                                               1 if ceil_mode else 0, 1 if count_include_pad else 0, _stream()))
+                                               1 if ceil_mode else 0, 1 if count_include_pad else 0, stream()))
         return gx
 
     def upsample_add_forward(self, top, lat, out=None):
@@ -842,7 +829,7 @@ class HipBackend:
         h, w = top.shape[2:]
         out = self._pool_new(lat, lat.shape) if out is None else out
         (tp, tpitch), (lp, lpitch), (op, opitch) = self._pool_arg(top, 'top'), self._pool_arg(lat, 'lat'), self._pool_arg(out, 'out')
-        _lib.check(lib.lsn_upsample_add_forward(tp, tpitch, lp, lpitch, op, opitch, B, h, w, H, W, C, _stream()))
+        _lib.check(lib.lsn_upsample_add_forward(tp, tpitch, lp, lpitch, op, opitch, B, h, w, H, W, C, stream()))
         return out
 
     def upsample_add_backward(self, grad_out, top_shape, out=None, accumulate=False):
@@ -853,7 +840,7 @@ class HipBackend:
         assert out is not None or not accumulate
         gt = self._pool_new(grad_out, top_shape) if out is None else out
         (gp, gpitch), (tp, tpitch) = self._pool_arg(grad_out, 'grad_out'), self._pool_arg(gt, 'grad_top')
-        _lib.check(lib.lsn_upsample_add_backward(gp, gpitch, tp, tpitch, 1 if accumulate else 0, B, h, w, H, W, C, _stream()))
+        _lib.check(lib.lsn_upsample_add_backward(gp, gpitch, tp, tpitch, 1 if accumulate else 0, B, h, w, H, W, C, stream()))
         return gt
 
     def corner_pool_forward(self, mode, x, out=None, accumulate=False):
@@ -864,7 +851,7 @@ class HipBackend:
         y = self._pool_new(x, x.shape) if out is None else out
         (xp, xpitch), (yp, ypitch) = self._pool_arg(x, 'x'), self._pool_arg(y, 'y')
         _lib.check(lib.lsn_corner_pool_forward(self.CORNER_MODES[mode], xp, xpitch, yp, ypitch, 1 if accumulate else 0, B, H, W, C,
-                                               _stream()))
+                                               stream()))
         return y
 
     def corner_pool_backward(self, mode, x, grad_y, out=None, accumulate=False):
@@ -874,7 +861,7 @@ class HipBackend:
         gx = self._pool_new(x, x.shape) if out is None else out
         (xp, xpitch), (gp, gpitch), (dp, dpitch) = self._pool_arg(x, 'x'), self._pool_arg(grad_y, 'grad_y'), self._pool_arg(gx, 'grad_x')
         _lib.check(lib.lsn_corner_pool_backward(self.CORNER_MODES[mode], xp, xpitch, gp, gpitch, dp, dpitch, 1 if accumulate else 0,
-                                                B, H, W, C, _stream()))
+                                                B, H, W, C, stream()))
         return gx
 
     # ------------------------------------------------------------------ LSHead's cumulative offset rescaling
@@ -897,13 +884,13 @@ class HipBackend:
             B, _, H, W = off.shape
             L = lv[l]
             L.images, L.per_image = B, H * W * C
-            L.off, L.off_image_pitch = _ptr(off), (off.stride(0) if B > 1 else H * W * C)
+            L.off, L.off_image_pitch = ptr(off), (off.stride(0) if B > 1 else H * W * C)
             outs = [torch.empty((B, C, H, W), device=off.device, dtype=torch.float32, memory_format=_CL) for _ in range(3)]
             for k in range(3):
                 L.mh[k], L.mw[k] = mults[l][k]
                 L.out[k] = outs[k].data_ptr()
             res.append(outs)
-        _lib.check(lib.lsn_offset_chain_forward(n, lv, C, _stream()))
+        _lib.check(lib.lsn_offset_chain_forward(n, lv, C, stream()))
         return res
 
     def offset_chain_backward(self, shapes, device, mults, grads):
@@ -926,7 +913,7 @@ class HipBackend:
             goff = torch.empty((B, C, H, W), device=device, dtype=torch.float32, memory_format=_CL)
             L.goff = goff.data_ptr()
             res.append(goff)
-        _lib.check(lib.lsn_offset_chain_backward(n, lv, C, _stream()))
+        _lib.check(lib.lsn_offset_chain_backward(n, lv, C, stream()))
         return res
 
     def selftest_mfma(self, A, B, variant):
@@ -935,7 +922,7 @@ class HipBackend:
         M, K = A.shape
         N = B.shape[1]
         D = torch.empty(M, N, device=A.device, dtype=torch.float32)
-        _lib.check(lib.lsn_selftest_mfma(_ptr(A), _ptr(B), _ptr(D), M, N, K, variant, _stream()))
+        _lib.check(lib.lsn_selftest_mfma(ptr(A), ptr(B), ptr(D), M, N, K, variant, stream()))
         return D
 
 

@@ -7,8 +7,6 @@ live where they will still live next step (the all-reduce buckets of parallel/re
 hook hands the whole thing to the library: per element the same operations in the same rounding order, the clip
 coefficient formed on the device.  Anything else -- no buckets, Nesterov / dampening / maximize, another optimizer, a norm
 type other than 2, CPU tensors -- keeps the torch path."""
-import ctypes
-
 import torch
 
 from .. import _lib
@@ -103,9 +101,7 @@ class ClipSGD:
         lib = _lib.load()
         for q, grp in zip(self.groups, self.opt.param_groups):
             q.lr, q.momentum, q.weight_decay = float(grp['lr']), float(grp['momentum']), float(grp['weight_decay'])
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.lsn_clip_sgd_step(len(self.entries), ctypes.c_void_p(self.table.data_ptr()), self.chunks, len(self.groups),
-                                         self.groups, ctypes.c_float(self.max_norm), ctypes.c_void_p(self.ws.data_ptr()),
-                                         ctypes.c_void_p(self.stats.data_ptr()), stream))
+        _lib.check(lib.lsn_clip_sgd_step(len(self.entries), _lib.ptr(self.table), self.chunks, len(self.groups), self.groups,
+                                         self.max_norm, _lib.ptr(self.ws), _lib.ptr(self.stats), _lib.stream()))
         _conv.parameters_updated()      # the cached weight images of the convolutions are stale now
         return self.stats[0] if self.max_norm > 0 else None

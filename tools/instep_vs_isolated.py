@@ -10,7 +10,6 @@ Isolated, per distinct call signature, four arms on fresh random tensors:
     warm-epi  warm without the residual / gate operands of the epilogue (only for calls that have them)
     chain     the call behind another large kernel of the library on the same stream, no idle gap (dependent-kernel hand-over)
 """
-import ctypes
 import os
 import sys
 from collections import OrderedDict
@@ -71,9 +70,8 @@ class Replay:
         nb = lib.lsn_conv2d_prepared_bytes(k['kind'], k['C'], k['Co'], k['kh'], k['kw'], k['stride'], k['pad'], k['dil'])
         assert nb > 0, key
         self.img = torch.empty(nb, dtype=torch.uint8, device=dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.lsn_conv2d_prepare_weights(k['kind'], ctypes.c_void_p(self.w.data_ptr()), ctypes.c_void_p(self.img.data_ptr()),
-                                                  k['C'], k['Co'], k['kh'], k['kw'], k['stride'], k['pad'], k['dil'], st))
+        _lib.check(lib.lsn_conv2d_prepare_weights(k['kind'], _lib.ptr(self.w), _lib.ptr(self.img), k['C'], k['Co'], k['kh'], k['kw'],
+                                                  k['stride'], k['pad'], k['dil'], _lib.stream()))
         self.bias = torch.randn(k['Co'], device=dev, generator=g)
         self.t = []
         for (B, H, W) in self.lv:
@@ -97,21 +95,19 @@ class Replay:
         arr = (_lib.ConvLevel * n)()
         for i, ((B, H, W), (x, out, res, gate)) in enumerate(zip(self.lv, self.t)):
             L = arr[i]
-            L.x, L.out, L.B, L.H, L.W = x.data_ptr(), out.data_ptr(), B, H, W
-            L.residual = res.data_ptr() if (res is not None and epi) else None
-            L.gate = gate.data_ptr() if (gate is not None and epi) else None
+            L.x, L.out, L.B, L.H, L.W = _lib.ptr(x), _lib.ptr(out), B, H, W
+            L.residual, L.gate = (_lib.ptr(res), _lib.ptr(gate)) if epi else (None, None)
         return arr
 
     def call(self, lv):
         k = self.k
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         if k['kind'] == 0:
-            _lib.check(lib.lsn_conv2d_forward_prepared(len(self.lv), lv, ctypes.c_void_p(self.img.data_ptr()),
-                                                       ctypes.c_void_p(self.bias.data_ptr()), k['C'], k['xpitch'], k['Co'], k['kh'], k['kw'],
-                                                       k['stride'], k['pad'], k['dil'], k['relu'], st))
+            _lib.check(lib.lsn_conv2d_forward_prepared(len(self.lv), lv, _lib.ptr(self.img), _lib.ptr(self.bias), k['C'], k['xpitch'],
+                                                       k['Co'], k['kh'], k['kw'], k['stride'], k['pad'], k['dil'], k['relu'],
+                                                       _lib.stream()))
         else:
-            _lib.check(lib.lsn_conv2d_backward_data_prepared(len(self.lv), lv, ctypes.c_void_p(self.img.data_ptr()), k['C'], k['Co'],
-                                                             k['kh'], k['kw'], k['stride'], k['pad'], k['dil'], st))
+            _lib.check(lib.lsn_conv2d_backward_data_prepared(len(self.lv), lv, _lib.ptr(self.img), k['C'], k['Co'], k['kh'], k['kw'],
+                                                             k['stride'], k['pad'], k['dil'], _lib.stream()))
 
     def flops(self):
         k, px = self.k, 0
