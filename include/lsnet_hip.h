@@ -807,6 +807,30 @@ int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C,
                      int num_vectors, int kind, int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img,
                      int cand_cap, float *dets, float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream);
 
+/* LSCPVHead.get_bboxes for a batch in one call (lscpvnet_head.py:905-1090): lsn_decode_batch of kind 0 -- the same three
+ * launches, selection, candidate order, NMS, cand_cap contract and workspace (lsn_decode_workspace_bytes) -- with the corners
+ * of a candidate point's box verified before the box is rescaled, stored and counted into max_coordinate.  No vectors are
+ * written and a level's `vec` is not read (it may be NULL).
+ *   sources: n_sources <= 8 of lsn_decode_source: the corner heat-map LOGITS (B, 2, H, W) and sub-cell offsets (B, 4, H, W)
+ *     of a level of stride `stride`, each with its element strides (batch, channel, y, x), read in place; H, W >= 2;
+ *   verify_src[n_levels], host: the source of every level, or -1 for a level decoded as lsn_decode_batch decodes it.
+ * A verified level replaces (x1, y1) and (x2, y2) of the clamped box, each by: cell = floor(clamp(coordinate / stride, 0,
+ * W - 2 or H - 2)) (a NaN or infinite coordinate lands inside the map); the arg-max of sigmoid(heat-map) over the 2x2 window
+ * that starts at the cell, in row-major order, the first maximum winning and a NaN taking over (max_pool2d's rule); then
+ * (float(col) + offset_x[row, col]) * stride and (float(row) + offset_y[row, col]) * stride, clamped to the image.  The
+ * top-left corner reads heat-map channel 0 and offset channels (0, 1), the bottom-right one channel 1 and channels (2, 3).
+ * LSN_ERR_INVALID: a source smaller than 2 x 2, a verify_src entry outside [-1, n_sources). */
+typedef struct {
+    int H, W;
+    float stride;
+    const float *heat, *offset;
+    int64_t heat_strides[4], offset_strides[4];
+} lsn_decode_source;
+int lsn_decode_cpv_batch(int B, int n_levels, const lsn_decode_level *levels, int n_sources, const lsn_decode_source *sources,
+                         const int *verify_src, int C, const float *img_hw, const float *scale_factors, int nms_pre, float score_thr,
+                         float iou_thr, int class_agnostic, int max_per_img, int cand_cap, float *dets, int64_t *labels,
+                         int32_t *counts, void *workspace, lsn_stream_t stream);
+
 /* ---- corner-point verification: targets and losses of LSCPVHead (csrc/cpv.hip, arithmetic in csrc/cpv_rows.h) -------------
  * Reference: point_hm_assigner.py:8-166, gaussian_focal_loss.py:8-89, smooth_l1_loss.py:8-90, focal_loss.py:45-71.
  * Every call is asynchronous on `stream`, allocates nothing, reads nothing back, uses no atomic operation and gives the same

@@ -98,6 +98,13 @@ class DecodeLevel(ctypes.Structure):
                 ('cls_strides', ctypes.c_int64 * 4), ('box_strides', ctypes.c_int64 * 4), ('vec_strides', ctypes.c_int64 * 4)]
 
 
+class DecodeSource(ctypes.Structure):
+    c_name = 'lsn_decode_source'
+    _fields_ = [('H', ctypes.c_int), ('W', ctypes.c_int), ('stride', ctypes.c_float),
+                ('heat', ctypes.c_void_p), ('offset', ctypes.c_void_p),
+                ('heat_strides', ctypes.c_int64 * 4), ('offset_strides', ctypes.c_int64 * 4)]
+
+
 class CornerLevel(ctypes.Structure):
     c_name = 'lsn_corner_level'
     _fields_ = [('H', ctypes.c_int), ('W', ctypes.c_int), ('score', ctypes.c_void_p), ('offset', ctypes.c_void_p),
@@ -127,7 +134,7 @@ class ProfLaunch(ctypes.Structure):
 
 # the mirrors above, one per struct typedef of include/lsnet_hip.h (each names its typedef in `c_name`)
 STRUCTS = (Strides4, DcnShape, DcnLevel, OffsetChainLevel, WgradBnJob, SgdTensor, SgdGroup, ConvLevel, ConvWprep, GnLevel, GateJob,
-           DecodeLevel, CornerLevel, SemLevel, ProfEntry, ProfLaunch)
+           DecodeLevel, DecodeSource, CornerLevel, SemLevel, ProfEntry, ProfLaunch)
 
 
 def _signatures():
@@ -229,6 +236,7 @@ def _signatures():
         'lsn_corner_pool_backward': (i, [i, p, i, p, i, p] + [i] * 6 + [p]),
         'lsn_decode_workspace_bytes': (q, [i, i, P(DecodeLevel), i, i]),
         'lsn_decode_batch': (i, [i, i, P(DecodeLevel), i, p, p, i, i, i, f, f, i, i, i] + [p] * 6),
+        'lsn_decode_cpv_batch': (i, [i, i, P(DecodeLevel), i, P(DecodeSource), p, i, p, p, i, f, f, i, i, i] + [p] * 5),
         'lsn_corner_targets_workspace_bytes': (q, [i]),
         'lsn_corner_targets_batch': (i, [p, i, p, p, i, p, i, d] + [p] * 5),
         'lsn_corner_loss_workspace_bytes': (q, [i, i, P(CornerLevel)]),

@@ -44,7 +44,7 @@ UNIT_HEADERS = {
     'conv.hip': ['common.h', 'conv_kernels.h', 'conv_wgrad_kernels.h', 'prof.h'],
     'misc.hip': ['common.h', 'prof.h'], 'norm.hip': ['common.h', 'prof.h'], 'gconv.hip': ['common.h', 'prof.h'],
     'image.hip': ['common.h'], 'loss.hip': ['common.h', 'cross_iou_row.h'], 'assign.hip': ['common.h', 'assign_rows.h'],
-    'pool.hip': ['common.h', 'pool_rows.h'], 'decode.hip': ['common.h', 'decode_rows.h', 'prof.h'], 'cpv.hip': ['common.h', 'assign_rows.h', 'cpv_rows.h'],
+    'pool.hip': ['common.h', 'pool_rows.h'], 'decode.hip': ['common.h', 'decode_rows.h', 'pool_rows.h', 'prof.h'], 'cpv.hip': ['common.h', 'assign_rows.h', 'cpv_rows.h'],
 }
 # flags of single translation units, after FLAGS: target assignment, the detection decode and the corner-verification targets
 # and losses are separately rounded fp32 arithmetic (assign_rows.h, decode_rows.h, cpv_rows.h)

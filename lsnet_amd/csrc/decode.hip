@@ -23,8 +23,12 @@ namespace lsn {
 //      three barriers per KEPT box -- and the kept rows are written: box, score, label and the vectors, decoded here from the
 //      maps for the kept rows only.
 // Nothing is allocated, nothing read back.  counts[b] < 0: more than cand_cap candidates, the image's rows are undefined.
+// LSCPVHead.get_bboxes (lscpv_head.py; lscpvnet_head.py:905-1090) is the same three launches with one step changed: a level
+// with a verification source has the corners of each candidate point's box snapped to the source's corner heat-map
+// (decode_box_verified of decode_rows.h: 8 heat-map and 4 offset reads per point, no pooled map) before the box goes to
+// `slotbox` and into the coordinate maximum.  It writes no vectors (nv = 0).
 // ---------------------------------------------------------------------------------------------
-constexpr int DECODE_MAX_IMAGES = 64, DECODE_MAX_LEVELS = 8, DECODE_MAX_KEEP = 2048, DECODE_TILE = 4096;
+constexpr int DECODE_MAX_IMAGES = 64, DECODE_MAX_LEVELS = 8, DECODE_MAX_KEEP = 2048, DECODE_TILE = 4096, DECODE_MAX_SOURCES = 8;
 
 struct DecodeLv {
     const float *cls, *box, *vec;
@@ -37,8 +41,17 @@ struct DecodeLv {
     int K;          // slots of the level
 };
 
+struct DecodeSrc {
+    const float *heat, *off;   // corner heat-map logits (B, 2, H, W), sub-cell offsets (B, 4, H, W)
+    int64_t hs[4], os[4];      // element strides (batch, channel, y, x)
+    int H, W;
+    float stride;
+};
+
 struct DecodeArgs {
     DecodeLv lv[DECODE_MAX_LEVELS];
+    DecodeSrc src[DECODE_MAX_SOURCES];
+    int verify[DECODE_MAX_LEVELS];   // the level's verification source, -1: decoded as it is
     float img_hw[DECODE_MAX_IMAGES][2];
     float sf[DECODE_MAX_IMAGES][4];
     int B, L, C, nv, kind, S, keys_per_image, cap, cap2, max_keep, class_agnostic;
@@ -53,6 +66,7 @@ struct DecodeArgs {
     int64_t *labels;
     int *counts;
 };
+static_assert(sizeof(DecodeArgs) <= 4096, "DecodeArgs is passed to the kernels by value");
 
 // exclusive prefix sum over the 1024 threads of the workgroup; total: the sum.  tmp: 16 ints of LDS.
 __device__ __forceinline__ int decode_scan(int v, int *tmp, int &total)
@@ -181,22 +195,32 @@ __global__ __launch_bounds__(256) void decode_candidates_kernel(const DecodeArgs
     for (int c = 0; c < a.C; ++c) {
         const float score = decode_sigmoid(decode_at(cm, c, y, x));
         if (!(score > a.score_thr)) continue;
-        if (!any) {
-            any = true;
-            float box[4];
-            decode_box(decode_map(lv.box, lv.bs, b), a.kind == DECODE_VECTORS, a.nv, y, x, decode_geom(a, b, l), box);
-            float *out = a.slotbox + ((size_t)b * a.S + s) * 4;
-            unsigned m = 0;
-            for (int i = 0; i < 4; ++i) {
-                out[i] = box[i];
-                const unsigned bits = box[i] > 0.f ? __float_as_uint(box[i]) : 0u;
-                m = bits > m ? bits : m;
-            }
-            atomicMax(&a.maxc[b], m);
-        }
+        any = true;
         const int idx = atomicAdd(&a.cnt[b], 1);
         if (idx < a.cap) a.cand[(size_t)b * a.cap2 + idx] = decode_order_key(score, (uint32_t)s * (uint32_t)a.C + (uint32_t)c);
     }
+    if (!any) return;
+    // the point's box, once and behind the class loop: the lanes of a wave meet their first candidate at different classes, and
+    // inside the loop the wave would walk the decode (and a verification's chain of dependent reads) once per such class
+    float box[4];
+    const int v = a.verify[l];
+    if (v < 0) {
+        decode_box(decode_map(lv.box, lv.bs, b), a.kind == DECODE_VECTORS, a.nv, y, x, decode_geom(a, b, l), box);
+    } else {
+        const DecodeSrc &sr = a.src[v];
+        DecodeCorner c;
+        c.heat = decode_map(sr.heat, sr.hs, b), c.off = decode_map(sr.off, sr.os, b);
+        c.H = sr.H, c.W = sr.W, c.stride = sr.stride;
+        decode_box_verified(decode_map(lv.box, lv.bs, b), y, x, decode_geom(a, b, l), &c, box);
+    }
+    float *out = a.slotbox + ((size_t)b * a.S + s) * 4;
+    unsigned m = 0;
+    for (int i = 0; i < 4; ++i) {
+        out[i] = box[i];
+        const unsigned bits = box[i] > 0.f ? __float_as_uint(box[i]) : 0u;
+        m = bits > m ? bits : m;
+    }
+    atomicMax(&a.maxc[b], m);
 }
 
 // one compare-exchange step of the bitonic network on words i and i + j of `w`; gi: the global index of word i
@@ -365,43 +389,33 @@ static int decode_check_sizes(int B, int L, const lsn_decode_level *levels, int 
     return LSN_OK;
 }
 
-}  // namespace lsn
-
-extern "C" {
-
-int64_t lsn_decode_workspace_bytes(int B, int n_levels, const lsn_decode_level *levels, int nms_pre, int cand_cap)
+// Both entry points after their own argument checks.  sources / verify: the corner verification of lsn_decode_cpv_batch (none:
+// every level is decoded as it is); num_vectors = 0 and vecs = null: no vector columns.
+static int decode_launch(int B, int n_levels, const lsn_decode_level *levels, int n_sources, const lsn_decode_source *sources,
+                         const int *verify, int C, const float *img_hw, const float *scale_factors, int num_vectors, int kind,
+                         int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img, int cand_cap, float *dets,
+                         float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream)
 {
-    using namespace lsn;
-    if (decode_check_sizes(B, n_levels, levels, cand_cap) != LSN_OK) return -1;
-    DecodePlan p;
-    if (!decode_plan(B, n_levels, levels, nms_pre, cand_cap, p, nullptr)) {
-        fail(LSN_ERR_INVALID, "decode: level sizes out of range");
-        return -1;
-    }
-    return (int64_t)p.bytes;
-}
-
-int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C, const float *img_hw, const float *scale_factors,
-                     int num_vectors, int kind, int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img,
-                     int cand_cap, float *dets, float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream)
-{
-    using namespace lsn;
-    if (int rc = decode_check_sizes(B, n_levels, levels, cand_cap)) return rc;
     LSN_CHECK(C >= 1, "decode: %d classes", C);
-    LSN_CHECK(kind == DECODE_BBOX || kind == DECODE_VECTORS || kind == DECODE_POSE_BBOX, "decode: unknown kind %d", kind);
-    LSN_CHECK(num_vectors >= 1 && (kind != DECODE_BBOX || num_vectors == 4), "decode: num_vectors %d (kind bbox has 4)", num_vectors);
     LSN_CHECK(max_per_img >= 1 && max_per_img <= DECODE_MAX_KEEP, "decode: max_per_img %d (1..%d)", max_per_img, DECODE_MAX_KEEP);
-    LSN_CHECK(img_hw && scale_factors && dets && vecs && labels && counts && workspace, "decode: null argument");
-    static thread_local DecodeArgs A;   // 2.9 KB, passed to the kernels by value
+    LSN_CHECK(img_hw && scale_factors && dets && labels && counts && workspace, "decode: null argument");
+    static thread_local DecodeArgs A;   // 3.7 KB, passed to the kernels by value
     DecodePlan p;
     LSN_CHECK(decode_plan(B, n_levels, levels, nms_pre, cand_cap, p, &A), "decode: level sizes out of range");
     LSN_CHECK((long long)p.S * C <= 0xffffffffll, "decode: %d slots x %d classes do not fit a 32-bit candidate id", p.S, C);
     for (int l = 0; l < n_levels; ++l) {
         const lsn_decode_level &s = levels[l];
-        LSN_CHECK(s.cls && s.box && s.vec, "decode: level %d has a null map", l);
+        LSN_CHECK(s.cls && s.box && (s.vec || !vecs), "decode: level %d has a null map", l);
         DecodeLv &d = A.lv[l];
         d.cls = s.cls, d.box = s.box, d.vec = s.vec, d.H = s.H, d.W = s.W, d.stride = s.stride;
         for (int i = 0; i < 4; ++i) d.cs[i] = s.cls_strides[i], d.bs[i] = s.box_strides[i], d.vs[i] = s.vec_strides[i];
+        A.verify[l] = verify ? verify[l] : -1;
+    }
+    for (int k = 0; k < n_sources; ++k) {
+        const lsn_decode_source &s = sources[k];
+        DecodeSrc &d = A.src[k];
+        d.heat = s.heat, d.off = s.offset, d.H = s.H, d.W = s.W, d.stride = s.stride;
+        for (int i = 0; i < 4; ++i) d.hs[i] = s.heat_strides[i], d.os[i] = s.offset_strides[i];
     }
     for (int b = 0; b < B; ++b) {
         A.img_hw[b][0] = img_hw[2 * b], A.img_hw[b][1] = img_hw[2 * b + 1];
@@ -427,6 +441,56 @@ int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C,
     hipLaunchKernelGGL(decode_nms_kernel, dim3(B), dim3(1024), 0, st, A);
     LSN_HIP(hipGetLastError());
     return LSN_OK;
+}
+
+}  // namespace lsn
+
+extern "C" {
+
+int64_t lsn_decode_workspace_bytes(int B, int n_levels, const lsn_decode_level *levels, int nms_pre, int cand_cap)
+{
+    using namespace lsn;
+    if (decode_check_sizes(B, n_levels, levels, cand_cap) != LSN_OK) return -1;
+    DecodePlan p;
+    if (!decode_plan(B, n_levels, levels, nms_pre, cand_cap, p, nullptr)) {
+        fail(LSN_ERR_INVALID, "decode: level sizes out of range");
+        return -1;
+    }
+    return (int64_t)p.bytes;
+}
+
+int lsn_decode_batch(int B, int n_levels, const lsn_decode_level *levels, int C, const float *img_hw, const float *scale_factors,
+                     int num_vectors, int kind, int nms_pre, float score_thr, float iou_thr, int class_agnostic, int max_per_img,
+                     int cand_cap, float *dets, float *vecs, int64_t *labels, int32_t *counts, void *workspace, lsn_stream_t stream)
+{
+    using namespace lsn;
+    if (int rc = decode_check_sizes(B, n_levels, levels, cand_cap)) return rc;
+    LSN_CHECK(kind == DECODE_BBOX || kind == DECODE_VECTORS || kind == DECODE_POSE_BBOX, "decode: unknown kind %d", kind);
+    LSN_CHECK(num_vectors >= 1 && (kind != DECODE_BBOX || num_vectors == 4), "decode: num_vectors %d (kind bbox has 4)", num_vectors);
+    LSN_CHECK(vecs, "decode: null argument");
+    return decode_launch(B, n_levels, levels, 0, nullptr, nullptr, C, img_hw, scale_factors, num_vectors, kind, nms_pre, score_thr,
+                         iou_thr, class_agnostic, max_per_img, cand_cap, dets, vecs, labels, counts, workspace, stream);
+}
+
+int lsn_decode_cpv_batch(int B, int n_levels, const lsn_decode_level *levels, int n_sources, const lsn_decode_source *sources,
+                         const int *verify_src, int C, const float *img_hw, const float *scale_factors, int nms_pre, float score_thr,
+                         float iou_thr, int class_agnostic, int max_per_img, int cand_cap, float *dets, int64_t *labels,
+                         int32_t *counts, void *workspace, lsn_stream_t stream)
+{
+    using namespace lsn;
+    if (int rc = decode_check_sizes(B, n_levels, levels, cand_cap)) return rc;
+    LSN_CHECK(n_sources >= 0 && n_sources <= DECODE_MAX_SOURCES, "decode: %d corner sources (0..%d)", n_sources, DECODE_MAX_SOURCES);
+    LSN_CHECK(verify_src && (sources || n_sources == 0), "decode: null argument");
+    for (int s = 0; s < n_sources; ++s) {
+        LSN_CHECK(sources[s].H >= 2 && sources[s].W >= 2, "decode: corner source %d is %d x %d (at least 2 x 2)", s, sources[s].H,
+                  sources[s].W);
+        LSN_CHECK(sources[s].heat && sources[s].offset, "decode: corner source %d has a null map", s);
+    }
+    for (int l = 0; l < n_levels; ++l)
+        LSN_CHECK(verify_src[l] >= -1 && verify_src[l] < n_sources, "decode: level %d verifies against source %d of %d", l,
+                  verify_src[l], n_sources);
+    return decode_launch(B, n_levels, levels, n_sources, sources, verify_src, C, img_hw, scale_factors, 0, DECODE_BBOX, nms_pre,
+                         score_thr, iou_thr, class_agnostic, max_per_img, cand_cap, dets, nullptr, labels, counts, workspace, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // Row arithmetic of the detection decode -- LSHead.get_bboxes -> _get_bboxes_single -> multiclass_nms_lsvr -> batched_nms ->
 // nms of lsnet_amd/models/dense_heads/ls_head.py, core/post_processing.py and ops/nms.py (reference: lsnet_head.py:321-370,
 // 1439-1668, bbox_nms.py:60-99, nms_wrapper.py:119-157, nms_cpu.cpp:21-63) -- written once for the device kernels
-// (csrc/decode.hip) and, compiled by a host compiler, for the loop-nest check of tests/test_decode_host.py.
+// (csrc/decode.hip) and, compiled by a host compiler, for the loop-nest check of tests/test_decode_host.py.  The corner
+// verification of LSCPVHead.get_bboxes (lscpv_head.py; lscpvnet_head.py:953-1090) is the last section, checked the same way
+// by tests/test_decode_cpv_host.py.
 //
 // Every coordinate operation is one separately rounded fp32 operation, in the order of the torch statements: no fused
 // multiply-add.  The host side is compiled with -ffp-contract=off; on the device every product that feeds an addition passes
@@ -15,6 +17,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include "pool_rows.h"
 
 #if defined(__HIPCC__)
 #define LSN_DHD __host__ __device__ __forceinline__
@@ -93,10 +97,10 @@ struct DecodeGeom {
     float sf[4];                  // the image's scale factors (1 when rescale is off)
 };
 
-// The box of point (y, x): [x1, y1, x2, y2] after clamp and rescale.
+// The box of point (y, x): [x1, y1, x2, y2] after clamp and rescale (decode_box) or before the rescale (decode_box_clamped).
 //   extreme-point map (20 channels, landmarks top, left, bottom, right, centre): [x_left, y_top, x_right, y_bottom]
 //   vector map (4 * (nv + 1) channels, the last landmark is the centre): min / max over the nv vectors
-LSN_DHD void decode_box(const DecodeMap &m, int from_vectors, int nv, int y, int x, const DecodeGeom &g, float *box)
+LSN_DHD void decode_box_clamped(const DecodeMap &m, int from_vectors, int nv, int y, int x, const DecodeGeom &g, float *box)
 {
     const float ax = (float)x * g.stride, ay = (float)y * g.stride;
     float x1, y1, x2, y2;
@@ -110,10 +114,64 @@ LSN_DHD void decode_box(const DecodeMap &m, int from_vectors, int nv, int y, int
             x1 = decode_min(x1, vx), x2 = decode_max(x2, vx), y1 = decode_min(y1, vy), y2 = decode_max(y2, vy);
         }
     }
-    box[0] = decode_coord(x1, g.stride, ax, g.img_w, g.sf[0]);
-    box[1] = decode_coord(y1, g.stride, ay, g.img_h, g.sf[1]);
-    box[2] = decode_coord(x2, g.stride, ax, g.img_w, g.sf[2]);
-    box[3] = decode_coord(y2, g.stride, ay, g.img_h, g.sf[3]);
+    box[0] = decode_clamp(decode_mul(x1, g.stride) + ax, g.img_w);
+    box[1] = decode_clamp(decode_mul(y1, g.stride) + ay, g.img_h);
+    box[2] = decode_clamp(decode_mul(x2, g.stride) + ax, g.img_w);
+    box[3] = decode_clamp(decode_mul(y2, g.stride) + ay, g.img_h);
+}
+
+LSN_DHD void decode_box(const DecodeMap &m, int from_vectors, int nv, int y, int x, const DecodeGeom &g, float *box)
+{
+    decode_box_clamped(m, from_vectors, nv, y, x, g, box);
+    for (int i = 0; i < 4; ++i) box[i] = box[i] / g.sf[i];      // (the operations of decode_coord, in its order)
+}
+
+// ---- corner verification (LSCPVHead._get_bboxes_single and _snap_to_corner; reference: lscpvnet_head.py:953-1090) ----
+// A level with a verification source replaces each corner of its clamped, not yet rescaled box by the strongest corner
+// response near it: the cell of the corner on the source's grid, the arg-max of sigmoid(heat-map) over the 2x2 window that
+// starts at that cell (max_pool2d, kernel 2, stride 1: scan order, tie and NaN rule are pool_max_takes of pool_rows.h), and
+// that cell plus its predicted sub-cell offset, * the source's stride, clamped to the image.  The top-left corner reads
+// heat-map channel 0 and offset channels (0, 1), the bottom-right corner channel 1 and offset channels (2, 3).
+struct DecodeCorner {
+    DecodeMap heat, off;   // one image's (2, H, W) logits and (4, H, W) offsets
+    int H, W;              // both >= 2
+    float stride;
+};
+
+// floor(clamp(v / s, 0, n - 2)) as an index: inside [0, n - 2] for every v, a NaN or an infinity included (the reference's
+// index for a NaN coordinate is undefined; this one never leaves the map)
+LSN_DHD int decode_corner_cell(float v, float s, int n)
+{
+    const float hi = (float)(n - 2);
+    const float c = floorf(decode_clamp(v / s, hi));
+    return c > 0.f ? (c < hi ? (int)c : n - 2) : 0;
+}
+
+// corner k (0: top-left, 1: bottom-right) at the clamped (x, y) -> the snapped corner, clamped to the image
+LSN_DHD void decode_snap(const DecodeCorner &c, int k, float x, float y, float img_w, float img_h, float *ox, float *oy)
+{
+    const int cx = decode_corner_cell(x, c.stride, c.W), cy = decode_corner_cell(y, c.stride, c.H);
+    int col = cx, row = cy;
+    float best = -INFINITY;
+    for (int dy = 0; dy < 2; ++dy)
+        for (int dx = 0; dx < 2; ++dx) {
+            const float v = decode_sigmoid(decode_at(c.heat, k, cy + dy, cx + dx));
+            if (pool_max_takes(v, best)) best = v, col = cx + dx, row = cy + dy;
+        }
+    *ox = decode_clamp(decode_mul((float)col + decode_at(c.off, 2 * k, row, col), c.stride), img_w);
+    *oy = decode_clamp(decode_mul((float)row + decode_at(c.off, 2 * k + 1, row, col), c.stride), img_h);
+}
+
+// The box of point (y, x) of an extreme-point map, its corners verified against `src` (null: the level is decoded as it is,
+// the bits of decode_box): clamp, snap, and only then / scale.
+LSN_DHD void decode_box_verified(const DecodeMap &m, int y, int x, const DecodeGeom &g, const DecodeCorner *src, float *box)
+{
+    decode_box_clamped(m, 0, 4, y, x, g, box);
+    if (src) {
+        decode_snap(*src, 0, box[0], box[1], g.img_w, g.img_h, &box[0], &box[1]);
+        decode_snap(*src, 1, box[2], box[3], g.img_w, g.img_h, &box[2], &box[3]);
+    }
+    for (int i = 0; i < 4; ++i) box[i] = box[i] / g.sf[i];
 }
 
 // Column i of the output vectors of point (y, x).

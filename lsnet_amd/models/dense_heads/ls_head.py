@@ -840,11 +840,9 @@ class LSHead(nn.Module):
         return 0 < cfg.max_per_img <= 2048 and 0 < num_imgs <= 64 and num_imgs == cls_scores[0].shape[0] and \
             len(cls_scores) <= 8 and all(t.dtype == torch.float32 and t.is_cuda for maps in (cls_scores,) + tuple(sources) for t in maps)
 
-    def _decode_native(self, cls_scores, sources, img_metas, cfg, rescale):
-        box_src, vec_src = sources
-        backend = get_backend(cls_scores[0])
-        levels = [(c.detach(), b.detach(), v.detach(), self.point_strides[i])
-                  for i, (c, b, v) in enumerate(zip(cls_scores, box_src, vec_src))]
+    @staticmethod
+    def _decode_scale_factors(img_metas, rescale):
+        """Four fp32 factors per image for the library's decode calls."""
         sfs = []
         for meta in img_metas:
             sf = np.ones(4, np.float32)             # x / 1.0f is exact: no rescale
@@ -852,6 +850,14 @@ class LSHead(nn.Module):
                 sf = np.atleast_1d(np.asarray(meta['scale_factor'], dtype=np.float32))
                 sf = np.tile(sf, 4)[:4] if sf.size < 4 else sf
             sfs.append(sf)
+        return sfs
+
+    def _decode_native(self, cls_scores, sources, img_metas, cfg, rescale):
+        box_src, vec_src = sources
+        backend = get_backend(cls_scores[0])
+        levels = [(c.detach(), b.detach(), v.detach(), self.point_strides[i])
+                  for i, (c, b, v) in enumerate(zip(cls_scores, box_src, vec_src))]
+        sfs = self._decode_scale_factors(img_metas, rescale)
         nms_cfg = cfg.nms
         return backend.decode_batch(levels, [meta['img_shape'][:2] for meta in img_metas], sfs, self.num_vectors,
                                     backend.DECODE_KINDS[self.task], cfg.get('nms_pre', -1), float(cfg.score_thr),

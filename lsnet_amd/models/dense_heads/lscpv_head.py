@@ -20,7 +20,9 @@ gather); the additions follow its rules: level-batched launches, no data-depende
 The targets and the three losses of the additions run as kernels of the library (csrc/cpv.hip: `lsn_corner_targets_batch`,
 `lsn_corner_loss_*`, `lsn_sep_focal_*`) when the tensors are fp32 on the device and the configured losses are exactly
 GaussianFocalLoss / SmoothL1Loss / SEPFocalLoss with reduction 'mean'; everything else -- host tensors, other dtypes,
-other losses, LSNET_NATIVE_CPV=0 -- runs the torch statements below, which are also the checker of those kernels."""
+other losses, LSNET_NATIVE_CPV=0 -- runs the torch statements below, which are also the checker of those kernels.  `get_bboxes`
+with NMS is one call of the library as well (csrc/decode.hip: `lsn_decode_cpv_batch`, the corner verification inside the candidates
+kernel; LSNET_NATIVE_DECODE=0 and everything the call does not take run the statements of `_get_bboxes_single`)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -34,6 +36,8 @@ from ...ops.corner_pool import BRPool, TLPool
 from ...ops.group_norm import GroupNorm
 from ..builder import HEADS, build_loss
 from ..losses.cpv_losses import GaussianFocalLoss, SEPFocalLoss, SmoothL1Loss
+from ...ops.backend import get_backend
+from . import ls_head
 from .ls_head import DCNConvModule, LSHead
 
 
@@ -313,18 +317,55 @@ class LSCPVHead(LSHead):
     # ----------------------------------------------------------------------------------- decoding
     def get_bboxes(self, cls_scores, bbox_pts_preds_init, bbox_pts_preds_refine, hm_scores, hm_offsets, sem_scores,
                    img_metas, cfg=None, rescale=False, nms=True):
-        """lscpvnet_head.py:905-951"""
+        """lscpvnet_head.py:905-951.  With NMS, fp32 device tensors and both verification levels at least 2 x 2 the library
+        decodes the batch in one call (lsn_decode_cpv_batch) and `counts` is the one host read; an image above the candidate
+        cap, and every other call, runs the torch statements of _get_bboxes_single."""
         assert len(cls_scores) == len(bbox_pts_preds_refine)
-        box_maps = [self.extreme_points2bbox(p) for p in bbox_pts_preds_refine]
-        device = cls_scores[0].device
-        points = [self.point_generators[i].grid_points(cls_scores[i].shape[-2:], self.point_strides[i], device)
-                  for i in range(len(cls_scores))]
+        cfg = self.test_cfg if cfg is None else cfg
+        padded, counts = None, [-1] * len(img_metas)       # a negative count: the image takes the torch statements
+        if nms and self._native_cpv_decode_ok(cls_scores, bbox_pts_preds_refine, hm_scores, hm_offsets, cfg, len(img_metas)):
+            padded = self._decode_cpv_native(cls_scores, bbox_pts_preds_refine, hm_scores, hm_offsets, img_metas, cfg, rescale)
+            counts = padded[2].cpu().tolist()
+        box_maps = points = None
         results = []
         for i, meta in enumerate(img_metas):
+            if counts[i] >= 0:
+                results.append((padded[0][i, :counts[i]], padded[1][i, :counts[i]]))
+                continue
+            if box_maps is None:
+                box_maps = [self.extreme_points2bbox(p) for p in bbox_pts_preds_refine]
+                device = cls_scores[0].device
+                points = [self.point_generators[l].grid_points(cls_scores[l].shape[-2:], self.point_strides[l], device)
+                          for l in range(len(cls_scores))]
             results.append(self._get_bboxes_single([c[i].detach() for c in cls_scores], [m[i].detach() for m in box_maps],
                                                    [h[i].detach() for h in hm_scores], [h[i].detach() for h in hm_offsets],
                                                    points, meta['img_shape'], meta['scale_factor'], cfg, rescale, nms))
         return results
+
+    @staticmethod
+    def _verify_sources(num_levels):
+        """The verification source of every level: none for level 0, the stride-8 maps for levels 1 and 2, the stride-16 maps
+        above (_get_bboxes_single)."""
+        return [-1 if l == 0 else (0 if l in (1, 2) else 1) for l in range(num_levels)]
+
+    def _native_cpv_decode_ok(self, cls_scores, bbox_refine, hm_scores, hm_offsets, cfg, num_imgs):
+        """LSHead's conditions for its maps, and the two corner levels fp32 on the device and at least 2 x 2."""
+        srcs = min(2, len(hm_scores))
+        if not self._native_decode_ok(cls_scores, (bbox_refine, hm_scores[:srcs], hm_offsets[:srcs]), cfg, num_imgs):
+            return False
+        return hasattr(get_backend(cls_scores[0]), 'decode_cpv_batch') and len(hm_offsets) >= srcs and \
+            all(min(h.shape[-2:]) >= 2 for h in hm_scores[:srcs])
+
+    def _decode_cpv_native(self, cls_scores, bbox_refine, hm_scores, hm_offsets, img_metas, cfg, rescale):
+        backend = get_backend(cls_scores[0])
+        levels = [(c.detach(), b.detach(), self.point_strides[l]) for l, (c, b) in enumerate(zip(cls_scores, bbox_refine))]
+        sources = [(hm_scores[s].detach(), hm_offsets[s].detach(), self.point_strides[s]) for s in range(min(2, len(hm_scores)))]
+        nms_cfg = cfg.nms
+        return backend.decode_cpv_batch(levels, sources, self._verify_sources(len(levels)),
+                                        [meta['img_shape'][:2] for meta in img_metas],
+                                        self._decode_scale_factors(img_metas, rescale), cfg.get('nms_pre', -1),
+                                        float(cfg.score_thr), float(nms_cfg['iou_thr']),
+                                        bool(nms_cfg.get('class_agnostic', False)), int(cfg.max_per_img), ls_head.DECODE_CAND_CAP)
 
     def _snap_to_corner(self, score_map, x, y, stride):
         """Corner verification of one corner type: the cell (x, y)/stride floor-ed, the arg-max of the 2x2 window
@@ -358,8 +399,8 @@ class LSCPVHead(LSHead):
             y1 = bboxes[:, 1].clamp(min=0, max=img_shape[0])
             x2 = bboxes[:, 2].clamp(min=0, max=img_shape[1])
             y2 = bboxes[:, 3].clamp(min=0, max=img_shape[0])
-            if lvl > 0:
-                src = 0 if lvl in (1, 2) else 1                 # verify against the stride-8 or stride-16 corner maps
+            src = self._verify_sources(lvl + 1)[lvl]            # verify against the stride-8 or stride-16 corner maps
+            if src >= 0:
                 stride = self.point_strides[src]
                 off = hm_offsets[src].permute(1, 2, 0)
                 cx1, cy1 = self._snap_to_corner(hm_scores[src][0], x1, y1, stride)

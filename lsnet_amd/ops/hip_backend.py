@@ -507,6 +507,54 @@ class HipBackend:
                                         vecs.data_ptr(), labels.data_ptr(), counts.data_ptr(), ws.data_ptr(), stream()))
         return dets, vecs, labels, counts
 
+    def decode_cpv_batch(self, levels, sources, verify_src, img_hw, scale_factors, nms_pre, score_thr, iou_thr, class_agnostic,
+                         max_per_img, cand_cap):
+        """LSCPVHead.get_bboxes for a batch in one call (lsn_decode_cpv_batch).  levels: (cls (B, C, H, W), 20-channel
+        extreme-point map, stride) per level; sources: (corner heat-map logits (B, 2, H, W), offsets (B, 4, H, W), stride) per
+        verification source, each at least 2 x 2; verify_src: per level the index of its source or -1; float32 device
+        tensors of any strides, read in place.  -> (dets (B, max_per_img, 5), labels (B, max_per_img) int64, counts (B,)
+        int32) as decode_batch returns them."""
+        lib = _lib.load()
+        B, C = levels[0][0].shape[:2]
+        dev = levels[0][0].device
+
+        def same(t, what, like, channels=None):
+            _f32(t, what)
+            if t.dim() != 4 or t.shape[0] != B or t.shape[2:] != like.shape[2:] or t.device != dev or \
+                    (channels is not None and t.shape[1] != channels):
+                raise ValueError(f'decode_cpv_batch: {what} of shape {tuple(t.shape)} beside {tuple(like.shape)}')
+        arr = (_lib.DecodeLevel * len(levels))()
+        for lv, (cls, box, stride) in zip(arr, levels):
+            same(cls, 'cls', cls, C)
+            same(box, 'box map', cls, 20)
+            lv.H, lv.W, lv.stride = cls.shape[2], cls.shape[3], float(stride)
+            lv.cls, lv.box, lv.vec = cls.data_ptr(), box.data_ptr(), None
+            lv.cls_strides[:], lv.box_strides[:] = cls.stride(), box.stride()
+        src = (_lib.DecodeSource * max(1, len(sources)))()
+        for sr, (heat, off, stride) in zip(src, sources):
+            same(heat, 'corner heat-map', heat, 2)
+            same(off, 'corner offsets', heat, 4)
+            sr.H, sr.W, sr.stride = heat.shape[2], heat.shape[3], float(stride)
+            sr.heat, sr.offset = heat.data_ptr(), off.data_ptr()
+            sr.heat_strides[:], sr.offset_strides[:] = heat.stride(), off.stride()
+        if len(verify_src) != len(levels):
+            raise ValueError(f'decode_cpv_batch: {len(verify_src)} verification entries for {len(levels)} levels')
+        verify = (ctypes.c_int * len(levels))(*[int(v) for v in verify_src])
+        hw = (ctypes.c_float * (2 * B))(*[float(v) for p in img_hw for v in p])
+        sf = (ctypes.c_float * (4 * B))(*[float(v) for p in scale_factors for v in p])
+        nbytes = int(lib.lsn_decode_workspace_bytes(B, len(levels), arr, int(nms_pre), int(cand_cap)))
+        if nbytes < 0:
+            _lib.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
+        labels = torch.empty((B, max_per_img), dtype=torch.int64, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.check(lib.lsn_decode_cpv_batch(B, len(levels), arr, len(sources), src, verify, C, hw, sf,
+                                            int(nms_pre), score_thr, iou_thr, int(bool(class_agnostic)), int(max_per_img),
+                                            int(cand_cap), dets.data_ptr(), labels.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                            stream()))
+        return dets, labels, counts
+
     # ------------------------------------------------------------------ k nearest per column (assigners)
     def topk_columns(self, x, k, seg_start, seg_len, largest=False):
         """x (P, G) float32 on the device -> (values, indices), both (nseg * k, G): per row segment the k smallest

@@ -7,11 +7,14 @@ against the torch statements (ls_head.NATIVE_DECODE off), on one GPU, on STORED 
              passes score_thr = 0.05 (up to 3350 candidates per image: 3 x 1000 + 273 + 77 selected points)
   bbox       C = 80; the same shift on ONE class per point (a fixed random choice), which gives the same number of
              candidates per image -- the shift on all 80 classes would make 268 000, far from any trained detector
+  bbox_cpv   the corner-verification head (LSCPVHead.get_bboxes, lsn_decode_cpv_batch), C = 80 with the shift of `bbox`; its
+             corner heat-maps and offsets are what the random-init head returned (profiles/native_decode_cpv.txt)
 
 default       device events around a loop of at least 0.5 s after warm-up, three alternating readings each way
               (profiles/native_decode_step.txt)
 --way torch   only the torch statements (this is what runs on a tree that has no native decode); --way native: only the kernels
 --readings N  N alternating readings each way instead of three
+--task NAME   only that task (default: all three)
 --trace       ten iterations each way and nothing else: run it under
               `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/bench_decode.py --trace` for kernel times
               (profiles/native_decode_kernel_stats.txt)"""
@@ -78,7 +81,8 @@ def ways():
 
 
 def main(trace):
-    for task in ('pose_kbox', 'bbox'):
+    tasks = [sys.argv[sys.argv.index('--task') + 1]] if '--task' in sys.argv else ['pose_kbox', 'bbox', 'bbox_cpv']
+    for task in tasks:
         head, outs, metas = stored_outputs(task)
 
         def run():
