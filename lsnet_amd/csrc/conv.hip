@@ -15,51 +15,25 @@
 // one-shot entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
-#include "../../include/lsnet_hip.h"
-#include "common.h"
 #include "conv_kernels.h"
 #include "conv_wgrad_kernels.h"
+#include "lib_state.h"
 #include "prof.h"
 
 namespace lsn {
 
-int split_np();   // dcn.hip: bf16 products per fp32 product of the current math mode (0: exact fp32)
 // bf16 products of these kernels; they have no fp32-MFMA variant: exact mode gets x6.  -1: no kernels (split_dispatch refuses)
-static int conv_np()
-{
-    switch (split_np()) {
-    case 0: return 6;
-    case 1: return 1;
-    case 3: return 3;
-    case 6: return 6;
-    default: return -1;
-    }
-}
+static int conv_np() { return math_np() == 0 ? 6 : math_np(); }
 static int conv_npl() { return split_npl(conv_np()); }
 
-// Library-owned scratch for the partial tiles of split reductions: ONE block PER STREAM (callers on different streams must
-// not share partial tiles), grown on demand.  A block that is outgrown is
-// RETIRED, not freed: a captured hipGraph may hold its address, and no device synchronisation is needed.
-// Growing while the stream is being captured is refused -- run the step eagerly once first (the graph wrapper's warm-up
-// calls do).  Host-side bookkeeping is not thread-safe (one Python thread drives the library).
-static long long g_stat[4] = {0, 0, 0, 0};
-void lib_stat(int which, long long add) { g_stat[which & 3] += add; }
-
-struct Scratch {
-    hipStream_t st;
-    float *p;
-    size_t floats;
-};
-static Scratch g_scr[16];
-static int g_nscr = 0;
 // ---- deferred weight-gradient reduces (conv_wgrad_kernels.h; include/lsnet_hip.h lsn_wgrad_defer) ----
-// While deferral is on for a stream, the partial tiles of its weight-gradient calls (part_buffer(..., keep = true)) come from an
-// ARENA that is not reused until the flush, and conv_wgrad_reduce() queues a descriptor instead of launching.
+// While deferral is on for a stream, the partial tiles of its weight-gradient calls (wgrad_part_buffer) come from the stream's
+// arena (lib_state.h), which is not reused until the flush, and conv_wgrad_reduce() queues a descriptor instead of launching.
 struct RJob {
     bool fold;
     const float *part, *part_b;
@@ -68,146 +42,21 @@ struct RJob {
     int nb, splits, splits_b, R, Co;
     WgFold f;
 };
-struct Arena {
-    hipStream_t st;
-    float *p;
-    size_t floats, used;
-    long long defer_mb;   // 0: off
-    std::vector<RJob> *jobs;
-};
-static Arena g_arena[16];
-static int g_narena = 0;
-static Arena *arena_of(hipStream_t st, bool create)
-{
-    for (int i = 0; i < g_narena; ++i)
-        if (g_arena[i].st == st) return &g_arena[i];
-    if (!create || g_narena == 16) return nullptr;
-    g_arena[g_narena] = Arena{st, nullptr, 0, 0, 0, new std::vector<RJob>()};
-    return &g_arena[g_narena++];
-}
 static int wgrad_flush(Arena *ar);
-
-// `floats` of arena space for the partial tiles of ONE weight-gradient call.  When the arena is full the queued reduces run
-// first (they consume every tile handed out so far, in stream order) and the arena starts over; while it is smaller than the
-// caller's limit (lsn_wgrad_defer) it is also replaced by a larger block -- nothing refers to the old one after the flush, so it is
-// freed once the stream has drained.  That synchronisation happens only while the arena is still finding its size (the first
-// step at the largest shape); in the steady state this function does pointer arithmetic and nothing else.
-static int arena_alloc(Arena *ar, size_t floats, float **p)
+// (never while the stream is being captured: a queued reduce is host state, a replay would not run it)
+static Arena *deferring(hipStream_t st)
 {
-    const size_t off = (ar->used + 63) & ~(size_t)63;
-    if (off + floats <= ar->floats) {
-        *p = ar->p + off;
-        ar->used = off + floats;
-        return 0;
-    }
-    if (int rc = wgrad_flush(ar)) return rc;
-    ar->used = 0;
-    const size_t limit = (size_t)ar->defer_mb << 18;   // MB -> floats
-    if (floats > ar->floats || ar->floats < limit) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(ar->st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(LSN_ERR_RUNTIME, "scratch would grow inside a stream capture: run the step eagerly once before capturing");
-        size_t want = 2 * ar->floats > off + floats ? 2 * ar->floats : off + floats;   // what this step has needed so far, at least doubled
-        if (want > limit + floats) want = limit + floats;
-        if (want < floats + floats / 4) want = floats + floats / 4;
-        want += (size_t)4 << 20;
-        if (ar->p) {
-            LSN_HIP(hipStreamSynchronize(ar->st));
-            lib_stat(STAT_BLOCKING_SYNCS, 1);
-            LSN_HIP(hipFree(ar->p));
-            lib_stat(STAT_HELD_BYTES, -(long long)(ar->floats * sizeof(float)));
-            ar->p = nullptr, ar->floats = 0;
-        }
-        float *np = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&np), want * sizeof(float)) != hipSuccess) {
-            //  no room for the arena: the queue is empty (flushed above), deferral ends for this stream and the call
-            // -- like every later one -- takes the per-stream scratch block with an immediate reduce
-            (void)hipGetLastError();
-            ar->defer_mb = 0, ar->used = 0;
-            return 1;
-        }
-        lib_stat(STAT_MALLOCS, 1), lib_stat(STAT_HELD_BYTES, (long long)(want * sizeof(float)));
-        ar->p = np, ar->floats = want;
-    }
-    *p = ar->p;
-    ar->used = floats;
-    return 0;
+    Arena *ar = arena_of(st);
+    return ar && ar->defer_mb > 0 && !stream_capturing(st) ? ar : nullptr;
 }
 
-static bool stream_capturing(hipStream_t st)
+int wgrad_part_buffer(size_t floats, float **p, hipStream_t st)
 {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-}
-
-static int part_buffer(size_t floats, float **p, hipStream_t st, bool keep = false)
-{
-    if (keep) {
-        // (never while the stream is being captured: a queued reduce is host state, a replay would not run it)
-        Arena *ar = arena_of(st, false);
-        if (ar && ar->defer_mb > 0 && !stream_capturing(st)) {
-            const int rc = arena_alloc(ar, floats, p);
-            if (rc != 1) return rc;   // 1: the arena could not be allocated, deferral is off now
-        }
+    if (Arena *ar = deferring(st)) {
+        const int rc = arena_alloc(ar, floats, p, wgrad_flush);
+        if (rc != 1) return rc;   // 1: the arena could not be allocated, deferral is off now
     }
-    Scratch *sc = nullptr;
-    for (int i = 0; i < g_nscr; ++i)
-        if (g_scr[i].st == st) sc = &g_scr[i];
-    if (!sc) {
-        if (g_nscr == 16) return fail(LSN_ERR_RUNTIME, "scratch: more than 16 streams use the library");
-        sc = &g_scr[g_nscr++];
-        *sc = Scratch{st, nullptr, 0};
-    }
-    if (floats > sc->floats) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(LSN_ERR_RUNTIME, "scratch would grow inside a stream capture: run the step eagerly once before capturing");
-        const size_t want = floats + floats / 4;
-        float *np = nullptr;
-        LSN_HIP(hipMalloc(reinterpret_cast<void **>(&np), want * sizeof(float)));
-        lib_stat(STAT_MALLOCS, 1), lib_stat(STAT_HELD_BYTES, (long long)(want * sizeof(float)));
-        sc->p = np, sc->floats = want;   // (the old block stays allocated: see above)
-    }
-    *p = sc->p;
-    return 0;
-}
-
-// Per-stream arrival counters of the stream-K tiles (conv_kernels.h ConvArgs): zeroed once, every launch leaves them zero.
-constexpr int SK_MAX_TILES = 4096;
-constexpr int LIB_TICKETS = 1024;   // behind the stream-K counters: self-resetting tickets of other kernels (norm.hip)
-struct SkCounters {
-    hipStream_t st;
-    unsigned *p;
-};
-static SkCounters g_skc[16];
-static int g_nskc = 0;
-static int sk_counters(unsigned **p, hipStream_t st)
-{
-    for (int i = 0; i < g_nskc; ++i)
-        if (g_skc[i].st == st) {
-            *p = g_skc[i].p;
-            return 0;
-        }
-    if (g_nskc == 16) return fail(LSN_ERR_RUNTIME, "scratch: more than 16 streams use the library");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(LSN_ERR_RUNTIME, "scratch would grow inside a stream capture: run the step eagerly once before capturing");
-    unsigned *np = nullptr;
-    LSN_HIP(hipMalloc(reinterpret_cast<void **>(&np), (SK_MAX_TILES + LIB_TICKETS) * sizeof(unsigned)));
-    lib_stat(STAT_MALLOCS, 1), lib_stat(STAT_HELD_BYTES, (long long)((SK_MAX_TILES + LIB_TICKETS) * sizeof(unsigned)));
-    LSN_HIP(hipMemsetAsync(np, 0, (SK_MAX_TILES + LIB_TICKETS) * sizeof(unsigned), st));
-    g_skc[g_nskc++] = SkCounters{st, np};
-    *p = np;
-    return 0;
-}
-
-// norm.hip: LIB_TICKETS zero-initialised, self-resetting ticket counters of this stream (last-arriver reductions)
-int lib_tickets(unsigned **p, hipStream_t st)
-{
-    unsigned *base = nullptr;
-    if (int rc = sk_counters(&base, st)) return rc;
-    *p = base + SK_MAX_TILES;
-    return 0;
+    return stream_scratch(floats, p, st);
 }
 
 // Work distribution of one launch (conv_kernels.h ConvArgs).  The chip holds 512 workgroups of these kernels at once, so
@@ -268,8 +117,7 @@ static int launch_conv_range(ConvArgs &a, int ks, int tile_base, int ntiles, hip
         if (a.sk_tiles > SK_MAX_TILES || ((long long)a.sk_tiles * a.kh * a.kw * cv_ncc(a.C) + 1) * a.sk_n >= ((long long)1 << 31))
             a.n_dp = ntw, a.sk_n = 0, a.sk_tiles = 0;
         if (a.sk_n) {
-            if (int rc = part_buffer((size_t)2 * a.sk_n * BM * BN, &a.sk_part, st)) return rc;
-            if (int rc = sk_counters(&a.sk_cnt, st)) return rc;
+            if (int rc = stream_sk_scratch((size_t)2 * a.sk_n * BM * BN, &a.sk_part, &a.sk_cnt, st)) return rc;
         }
     }
     a.ksplit = ks;
@@ -279,25 +127,19 @@ static int launch_conv_range(ConvArgs &a, int ks, int tile_base, int ntiles, hip
     a.part_pix0 = pix0, a.part_rows = rows;
     const size_t n = (size_t)rows * a.Co;
     if (ks > 1)
-        if (int rc = part_buffer(n * ks, &a.part, st)) return rc;
+        if (int rc = stream_scratch(n * ks, &a.part, st)) return rc;
     dim3 grid(a.n_dp + a.sk_n, 1, ks);
-    if (a.sk_n) {
-        auto k = conv_mm_kernel<TM, TN, WM, WN, NP, UNAL, FINE, TRANS, true>;
+    auto launch = [&](auto sk) -> int {   // sk: the stream-K form of the kernel
+        auto k = conv_mm_kernel<TM, TN, WM, WN, NP, UNAL, FINE, TRANS, decltype(sk)::value>;
         static bool attr_set = false;   // per instantiation
         if (!attr_set) {
             LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr_set = true;
         }
         hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);
-    } else {
-        auto k = conv_mm_kernel<TM, TN, WM, WN, NP, UNAL, FINE, TRANS, false>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);
-    }
+        return 0;
+    };
+    if (int rc = a.sk_n ? launch(std::true_type()) : launch(std::false_type())) return rc;
     if (ks > 1) {
         const int blocks = (int)((n / 4 + 255) / 256 < 1024 ? (n / 4 + 255) / 256 : 1024);
         const size_t o = (size_t)pix0 * a.Co;
@@ -717,8 +559,6 @@ static int prepare_weights(int kind, const float *w, void *prepared, int C, int 
 }
 
 // ---- weight / bias gradient (conv_wgrad_kernels.h) ----
-int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_b, float *gb, int nb, int splits, int splits_b,
-                      int accumulate, hipStream_t st);
 // (state of a folded-norm weight-gradient call, see conv_wgrad_reduce below)
 static thread_local const WgFoldJobs *g_wg_fold = nullptr;
 bool conv_wgrad_fold_pending() { return g_wg_fold != nullptr; }
@@ -740,7 +580,7 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     if (S < 1) S = 1;
     S *= nj;
     float *part = nullptr;
-    if (int rc = part_buffer((size_t)S * (nW + a.Co) + 16, &part, st, true)) return rc;
+    if (int rc = wgrad_part_buffer((size_t)S * (nW + a.Co) + 16, &part, st)) return rc;
     a.part = part;
     a.part_b = part + (((size_t)S * nW + 3) & ~(size_t)3);
     a.want_bias = gb != nullptr;
@@ -773,11 +613,9 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     return conv_wgrad_reduce(a.part, gw, nW, a.part_b, gb, a.Co, S, S, accumulate, st);
 }
 
-// dcn.hip: gw (+)= sum of `splits` partial gradients of n floats (n % 4 == 0), gb (+)= sum of splits_b partial rows of nb
-// With a BatchNorm fold pending (lsn_conv2d_backward_weight_bn set g_wg_fold for the duration of its weight-gradient
-// call) the reduce also applies the norm's scale and forms grad_gamma / grad_beta (conv_wgrad_reduce_bn_kernel); gb is then
-// the entry point's dummy bias gradient (it only makes the main kernels write the per-channel sums of g).
-
+// Lanes that share a float4 of the reduce: each sums PER_LANE partial tiles on its own before the xor-shuffles (>= PER_LANE / 2
+// loads per lane; a wave's lanes share 64 / LS elements).  Round-4 sweep (tools/ubench/wgrad_ab rule / bn, us per step of the layer
+// mix): 4: 3374 / 2945, 8: 3284 / 2729, 16: 3254 / 2650, 32: 3252 / 2642 -- fewer, longer lanes win until the loads in flight run out.
 static int reduce_ls(int splits)
 {
     constexpr int PER_LANE = 16;
@@ -786,14 +624,20 @@ static int reduce_ls(int splits)
     return LS;
 }
 
+// dcn.hip: gw (+)= sum of `splits` partial gradients of n floats (n % 4 == 0), gb (+)= sum of splits_b partial rows of nb
+// With a BatchNorm fold pending (lsn_conv2d_backward_weight_bn set g_wg_fold for the duration of its weight-gradient
+// call) the reduce also applies the norm's scale and forms grad_gamma / grad_beta (conv_wgrad_reduce_bn_kernel); gb is then
+// the entry point's dummy bias gradient (it only makes the main kernels write the per-channel sums of g).
 int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_b, float *gb, int nb, int splits, int splits_b,
                       int accumulate, hipStream_t st)
 {
-    Arena *ar = arena_of(st, false);
-    if (ar && ar->defer_mb > 0 && accumulate && !stream_capturing(st)) {
+    const int nj = wg_jobs();   // (splits / splits_b count ALL jobs' partial tiles)
+    if (g_wg_fold)
+        LSN_CHECK(part_b && nb > 0 && n % ((size_t)nb * 4) == 0 && splits % nj == 0 && splits_b % nj == 0,
+                  "conv2d backward-weight (folded norm): bad partial layout");
+    if (Arena *ar = accumulate ? deferring(st) : nullptr) {
         // queue instead of launching.  A gradient that already has a queued job is reduced first: two jobs of one launch must
         // not add onto the same addresses.
-        const int nj = g_wg_fold ? g_wg_fold->njobs : 1;
         bool clash = false;
         for (const RJob &q : *ar->jobs)
             for (int j = 0; j < nj; ++j) {
@@ -802,21 +646,13 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
             }
         if (clash)
             if (int rc = wgrad_flush(ar)) return rc;   // (the arena is NOT rewound here: this call's partial tiles are in it)
-        if (g_wg_fold) {
-            LSN_CHECK(part_b && nb > 0 && n % ((size_t)nb * 4) == 0 && splits % nj == 0 && splits_b % nj == 0,
-                      "conv2d backward-weight (folded norm): bad partial layout");
-            for (int j = 0; j < nj; ++j) {
-                RJob q = {};
-                q.fold = true;
-                q.part = part + (size_t)j * (splits / nj) * n, q.part_b = part_b + (size_t)j * (splits_b / nj) * nb;
-                q.gw = nj > 1 ? g_wg_fold->gw[j] : gw;
-                q.n = n, q.nb = nb, q.splits = splits / nj, q.splits_b = splits_b / nj, q.R = (int)(n / nb), q.Co = nb;
-                q.f = g_wg_fold->f[j];
-                ar->jobs->push_back(q);
-            }
-        } else {
+        for (int j = 0; j < nj; ++j) {   // (plain: one job, the caller's own pointers)
             RJob q = {};
-            q.fold = false, q.part = part, q.part_b = part_b, q.gw = gw, q.gb = gb, q.n = n, q.nb = nb, q.splits = splits, q.splits_b = splits_b;
+            q.fold = g_wg_fold != nullptr;
+            q.part = part + (size_t)j * (splits / nj) * n, q.part_b = q.fold ? part_b + (size_t)j * (splits_b / nj) * nb : part_b;
+            q.gw = nj > 1 ? g_wg_fold->gw[j] : gw, q.gb = q.fold ? nullptr : gb;
+            q.n = n, q.nb = nb, q.splits = splits / nj, q.splits_b = splits_b / nj;
+            if (q.fold) q.R = (int)(n / nb), q.Co = nb, q.f = g_wg_fold->f[j];
             ar->jobs->push_back(q);
         }
         if ((long long)(ar->used * sizeof(float)) > (ar->defer_mb << 20)) {
@@ -825,18 +661,8 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
         }
         return 0;
     }
-    int LS = 1;
-    // partial tiles a lane sums on its own before the xor-shuffles (LS = splits / PER_LANE lanes share a float4).  Round-4 sweep
-    // (tools/ubench/wgrad_ab rule / bn, us per step of the benchmark's layer mix): 4: 3374 / 2945, 8: 3284 / 2729,
-    // 16: 3254 / 2650, 32: 3252 / 2642 -- fewer, longer lanes win until the loads in flight run out.
-    constexpr int PER_LANE = 16;
-    while (LS < 64 && LS * PER_LANE <= splits) LS <<= 1;   // >= PER_LANE / 2 loads per lane; a wave's lanes share 64 / LS elements
+    const int LS = reduce_ls(splits / nj);
     if (g_wg_fold) {
-        const int nj = g_wg_fold->njobs;   // (splits / splits_b count ALL jobs' partial tiles)
-        LSN_CHECK(part_b && nb > 0 && n % ((size_t)nb * 4) == 0 && splits % nj == 0 && splits_b % nj == 0,
-                  "conv2d backward-weight (folded norm): bad partial layout");
-        LS = 1;
-        while (LS < 64 && LS * PER_LANE <= splits / nj) LS <<= 1;
         hipLaunchKernelGGL(conv_wgrad_reduce_bn_kernel, dim3(nb, nj), dim3(256), 0, st, part, gw, (int)(n / nb), nb, part_b,
                            splits / nj, splits_b / nj, accumulate, LS, *g_wg_fold);
         LSN_HIP(hipGetLastError());
@@ -893,17 +719,6 @@ static int wgrad_flush(Arena *ar)
     LSN_HIP(hipGetLastError());
     return 0;
 }
-
-// dcn.hip (stream-K pieces of the deformable forward): slots in this stream's scratch block and its tile counters
-int conv_sk_scratch(size_t floats, float **part, unsigned **cnt, hipStream_t st)
-{
-    if (int rc = part_buffer(floats, part, st)) return rc;
-    return sk_counters(cnt, st);
-}
-int conv_sk_max_tiles() { return SK_MAX_TILES; }
-
-// library-owned scratch (also for dcn.hip's weight-gradient pass): grows, never shrinks
-int conv_scratch(size_t floats, float **p, hipStream_t st) { return part_buffer(floats, p, st, true); }   // (weight-gradient passes of dcn.hip)
 
 // Returns 1 when the shape is not served here (more than nine taps, C % 4 != 0, 64-bit offsets): the caller keeps the
 // general kernel of dcn.hip.
@@ -970,29 +785,22 @@ static int prepare_weights_multi(int n, const lsn_conv_wprep *it, hipStream_t st
             return fail(LSN_ERR_UNSUPPORTED, "conv2d: weight too large for 32-bit buffer offsets");
         BnFold bn;
         if (int rc = bn_fold_of(p, &bn)) return rc;
+        auto add = [&](void *out, int Co, int K, int C, int flipT, const TapSub &ts) {
+            WfragJob j;
+            wfrag_job(j, p.w, reinterpret_cast<unsigned short *>(out), Co, K, C, flipT, ts, bn);
+            j.start = total;
+            total += wfrag_threads(j);
+            jobs.push_back(j);
+        };
         if (p.kind == 0) {
-            WfragJob j;
-            wfrag_job(j, p.w, reinterpret_cast<unsigned short *>(p.prepared), p.Co, p.kh * p.kw, p.C, 0, TapSub{}, bn);
-            j.start = total;
-            total += wfrag_threads(j);
-            jobs.push_back(j);
+            add(p.prepared, p.Co, p.kh * p.kw, p.C, 0, TapSub{});
         } else if (p.kind == 2) {
-            WfragJob j;
-            wfrag_job(j, p.w, reinterpret_cast<unsigned short *>(p.prepared), p.kh * p.kw * p.C, 1, p.Co, 1, TapSub{0, 1, 1, 0, 1, 1, 1}, bn);
-            j.start = total;
-            total += wfrag_threads(j);
-            jobs.push_back(j);
+            add(p.prepared, p.kh * p.kw * p.C, 1, p.Co, 1, TapSub{0, 1, 1, 0, 1, 1, 1});
         } else {
             BwdPlan pl;
             if (int rc = bwd_plan(p.C, p.Co, p.kh, p.kw, p.stride, p.pad, p.dil, &pl)) return rc;
-            for (int c = 0; c < pl.ncls; ++c) {
-                WfragJob j;
-                wfrag_job(j, p.w, reinterpret_cast<unsigned short *>(reinterpret_cast<unsigned char *>(p.prepared) + pl.cls[c].wf_off),
-                          p.C, p.kh * p.kw, p.Co, 1, pl.cls[c].ts, bn);
-                j.start = total;
-                total += wfrag_threads(j);
-                jobs.push_back(j);
-            }
+            for (int c = 0; c < pl.ncls; ++c)
+                add(reinterpret_cast<unsigned char *>(p.prepared) + pl.cls[c].wf_off, p.C, p.kh * p.kw, p.Co, 1, pl.cls[c].ts);
         }
     }
     if (jobs.empty()) return 0;
@@ -1028,14 +836,16 @@ extern "C" {
 int lsn_wgrad_defer(int max_mbytes, lsn_stream_t stream)
 {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    lsn::Arena *ar = lsn::arena_of(st, max_mbytes > 0);
-    if (!ar) return max_mbytes > 0 ? lsn::fail(LSN_ERR_RUNTIME, "scratch: more than 16 streams use the library") : 0;
+    lsn::Arena *ar = lsn::arena_of(st);
     if (max_mbytes > 0) {
+        if (int rc = lsn::arena_get(st, &ar)) return rc;
+        if (!ar->jobs) ar->jobs = new std::vector<lsn::RJob>();
         ar->jobs->clear();   // (a step that died half-way may have left descriptors behind: they are dropped, not run)
         ar->used = 0;
         ar->defer_mb = max_mbytes;
         return 0;
     }
+    if (!ar) return 0;
     const int rc = lsn::wgrad_flush(ar);
     ar->defer_mb = 0, ar->used = 0;
     return rc;
@@ -1043,18 +853,11 @@ int lsn_wgrad_defer(int max_mbytes, lsn_stream_t stream)
 
 int lsn_wgrad_flush(lsn_stream_t stream)
 {
-    lsn::Arena *ar = lsn::arena_of(reinterpret_cast<hipStream_t>(stream), false);
+    lsn::Arena *ar = lsn::arena_of(reinterpret_cast<hipStream_t>(stream));
     if (!ar) return 0;
     const int rc = lsn::wgrad_flush(ar);
     ar->used = 0;
     return rc;
-}
-
-int lsn_scratch_stats(long long *out4)
-{
-    LSN_CHECK(out4 != nullptr, "lsn_scratch_stats: NULL pointer");
-    for (int i = 0; i < 4; ++i) out4[i] = lsn::g_stat[i];
-    return 0;
 }
 
 int lsn_conv2d_backward_weight_bn(const float *x, const float *g, const float *w, const float *bn_gamma, const float *bn_mean,

@@ -4,9 +4,6 @@
 #include <limits.h>
 #include <string.h>
 
-#include <cstdlib>
-#include <cstring>
-#include <cstdio>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
@@ -14,63 +11,15 @@
 #include "dcn_kernels.h"
 #include "dcn_mm_kernels.h"
 #include "dcn_grouped_kernels.h"
+#include "lib_state.h"
 #include "prof.h"
 
 namespace lsn {
-
-static thread_local char g_err[640];
-char *err_buf() { return g_err; }
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 // optional phase-clock capture and kernel routing for tests / A/B runs (diagnostics only; see lsn_debug_phase_clocks)
 static long long *g_dbg_buf = nullptr;
 static int g_dbg_block = 0;
 static bool dbg_on(int bit) { return (g_dbg_block & bit) != 0; }   // bit: one of the LSN_DBG_* of lsnet_hip.h
-
-// arithmetic of the implicit-GEMM contractions: exact fp32 MFMA, or split-bf16 products (common.h)
-static int g_math_mode = -1;   // -1: not initialised (LSNET_MATH decides at first use)
-static int math_mode()
-{
-    if (g_math_mode < 0) {
-        const char *e = getenv("LSNET_MATH");
-        g_math_mode = (e && (!strcmp(e, "fp32") || !strcmp(e, "exact"))) ? LSN_MATH_FP32
-                      : (e && !strcmp(e, "bf16x3"))                       ? LSN_MATH_BF16X3
-                      : (e && !strcmp(e, "bf16"))                         ? LSN_MATH_BF16
-                                                                          : LSN_MATH_BF16X6;
-    }
-    return g_math_mode;
-}
-// bf16 products per fp32 product of the current mode (0: exact fp32 MFMA; -1: unknown, which split_dispatch refuses)
-static int math_np()
-{
-    switch (math_mode()) {
-    case LSN_MATH_FP32: return 0;
-    case LSN_MATH_BF16: return 1;
-    case LSN_MATH_BF16X3: return 3;
-    case LSN_MATH_BF16X6: return 6;
-    default: return -1;
-    }
-}
-int split_np() { return math_np(); }
-
-// ---- per-kernel launch timing (prof.h) ----
-static const char *const kProfNames[PROF_N] = {"dcn_fwd", "dcn_bwd_data", "dcn_wgrad", "conv_fwd", "conv_bwd_data",
-                                               "conv_wgrad", "norm", "gconv", "decode"};
-static unsigned g_prof_mask = 0;   // bit f: family f records events
-static std::vector<ProfRec> g_prof;
-bool prof_on(int fam) { return fam >= 0 && fam < 32 && ((g_prof_mask >> fam) & 1u); }
-void prof_push(const ProfRec &r) { g_prof.push_back(r); }
-static bool g_launch_log = false;
-static std::vector<LaunchRec> g_launches;
-bool launch_log_on() { return g_launch_log; }
-void launch_log_push(const LaunchRec &r) { g_launches.push_back(r); }
 
 static double dcn_flops(const DcnArgs &a)
 {
@@ -316,8 +265,6 @@ static bool mm_fwd_ok(const DcnArgs &a)
 // backward-data GEMM as a 1x1 convolution (conv.hip conv_mm_rows) + corner sums in the gather pass: every level that
 // wants offset / mask gradients must also want grad_input (its samples are then on the anchor lists); the fragment image
 // has to fit the caller's weight workspace (8 bytes per weight element, include/lsnet_hip.h)
-int conv_mm_rows(int n, const float *const *x, float *const *out, const int *rows, int Cr, int xpitch, int N,
-                 const unsigned short *wf, hipStream_t st);
 static bool mm_bwd_ok(const DcnArgs &a)
 {
     if (!mm_common_ok(a) || a.C % 4 != 0 || a.Co % 4 != 0) return false;
@@ -336,8 +283,6 @@ static bool mm_bwd_ok(const DcnArgs &a)
 // its second round runs one workgroup per CU, which has the matrix pipe to itself and finishes in ~0.65 of a round, so the
 // even split has little to return and the pieces' table rebuild and hand-over cost more.  Hence: launches of two rounds and
 // more only (the opposite of the dense kernel's rule, conv.hip sk_plan, whose short tiles lose to the longer prologue there).
-int conv_sk_scratch(size_t floats, float **part, unsigned **cnt, hipStream_t st);
-int conv_sk_max_tiles();
 static void dcn_sk_plan(int ntw, int Tall, DcnSk *sk)
 {
     sk->n_dp = ntw, sk->sk_n = 0, sk->sk_tiles = 0, sk->part = nullptr, sk->cnt = nullptr;
@@ -355,7 +300,7 @@ static void dcn_sk_plan(int ntw, int Tall, DcnSk *sk)
     const long long pieces = (long long)r * per_tile;
     const int ns = pieces < SLOTS ? (int)pieces : SLOTS;
     if (ns <= r) return;
-    if (r > conv_sk_max_tiles() || ((long long)r * Tall + 1) * ns >= ((long long)1 << 31)) return;
+    if (r > SK_MAX_TILES || ((long long)r * Tall + 1) * ns >= ((long long)1 << 31)) return;
     sk->n_dp = ntw - r, sk->sk_n = ns, sk->sk_tiles = r;
 }
 
@@ -368,7 +313,7 @@ static int launch_fwd_mm_cfg(const DcnArgs &a, hipStream_t st)
     DcnSk sk;
     dcn_sk_plan(blocks, a.kh * a.kw * (a.C / 32), &sk);
     if (!sk.sk_n) return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, false>, dim3(blocks), lds, st, a, a.wtp, a.wtp_bytes, sk);
-    if (int rc = conv_sk_scratch((size_t)2 * sk.sk_n * 64 * BN, &sk.part, &sk.cnt, st)) return rc;
+    if (int rc = stream_sk_scratch((size_t)2 * sk.sk_n * 64 * BN, &sk.part, &sk.cnt, st)) return rc;
     return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, true>, dim3(sk.n_dp + sk.sk_n), lds, st, a, a.wtp, a.wtp_bytes, sk);
 }
 
@@ -810,32 +755,21 @@ static int bwd_tap_groups(const DcnArgs &a)
 // gathers take the CUs from the weight gradient's workgroups instead of sharing them), -120 us on the pyramid launch,
 // 0.25 ms per step -- and two kernel families that can no longer be timed apart.  Removed.)
 struct SideStream {
-    hipStream_t main = nullptr, side = nullptr;
+    hipStream_t side = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
 };
-static SideStream g_side[16];
-static int g_nside = 0;
+static PerStream<SideStream> g_side;
 static int side_stream(hipStream_t st, SideStream **out)
 {
-    for (int i = 0; i < g_nside; ++i)
-        if (g_side[i].main == st) {
-            *out = &g_side[i];
-            return 0;
-        }
-    if (g_nside == 16) return fail(LSN_ERR_RUNTIME, "side streams: more than 16 streams use the library");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(LSN_ERR_RUNTIME, "side stream would be created inside a stream capture: run the step eagerly once before capturing");
-    SideStream &S = g_side[g_nside];
-    int lo = 0, hi = 0;
-    LSN_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi = the numerically lowest = most urgent
-    LSN_HIP(hipStreamCreateWithPriority(&S.side, hipStreamNonBlocking, hi));
-    LSN_HIP(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming));
-    LSN_HIP(hipEventCreateWithFlags(&S.join, hipEventDisableTiming));
-    S.main = st;
-    ++g_nside;
-    *out = &S;
-    return 0;
+    return g_side.get(st, "side streams", out, [&](SideStream &S) {
+        if (int rc = refuse_capture(st, "side stream would be created")) return rc;
+        int lo = 0, hi = 0;
+        LSN_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi = the numerically lowest = most urgent
+        LSN_HIP(hipStreamCreateWithPriority(&S.side, hipStreamNonBlocking, hi));
+        LSN_HIP(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming));
+        LSN_HIP(hipEventCreateWithFlags(&S.join, hipEventDisableTiming));
+        return 0;
+    });
 }
 
 // (Round 5 cut the launch into bands -- an anchor range per image of a grad_input map + the GEMM rows that scatter into it --
@@ -982,11 +916,6 @@ static int wgrad_vec_bits(const DcnArgs &a)
 }
 
 // ---- weight gradient on the kernels of dcn_mm_kernels.h: grad_output in fragment order, split partial tiles ----
-int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_b, float *gb, int nb, int splits, int splits_b,
-                      int accumulate, hipStream_t st);
-bool conv_wgrad_fold_pending();   // conv.hip: lsn_conv2d_backward_weight_bn is the caller
-int conv_scratch(size_t floats, float **p, hipStream_t st);
-
 // dense: a dense convolution's weight gradient (levels without offsets, no backward-data pass before this one): the
 // sampling table is built here, and the launch is accounted to the caller's family
 static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hipStream_t st, bool dense = false)
@@ -1011,7 +940,7 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
         tap_entries = (size_t)a.gtap_rows * K * a.dg;
     }
     float *base = nullptr;
-    if (int rc = conv_scratch(img_f + part_f + pb_f + meta_f + (tap_entries ? (tap_entries + 1) * (sizeof(Tap) / 4) : 0), &base, st))
+    if (int rc = wgrad_part_buffer(img_f + part_f + pb_f + meta_f + (tap_entries ? (tap_entries + 1) * (sizeof(Tap) / 4) : 0), &base, st))
         return rc;
     unsigned short *img = reinterpret_cast<unsigned short *>(base);
     float *part = base + img_f, *part_b = part + part_f;
@@ -1067,7 +996,7 @@ static int launch_wgrad_grouped(const DcnArgs &a_in, bool accumulate, hipStream_
         splits = cdiv(rows, per);
     }
     float *base = nullptr;
-    if (int rc = conv_scratch((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
+    if (int rc = wgrad_part_buffer((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
     float *part = base, *part_b = a.gb ? base + (((size_t)splits * nW + 3) & ~(size_t)3) : nullptr;
     ProfScope prof(PROF_WGRAD, a, st);
     const size_t lds = dcn_wgrad_grouped_lds_bytes(K, nch, nco);
@@ -1097,7 +1026,7 @@ static int launch_wgrad_split(const DcnArgs &a_in, const DcnRoute &r, bool accum
     const bool ordered = r.wgrad == WG_XN_ORDERED || r.wgrad == WG_FP32_ORDERED;
     if (ordered) {
         float *base = nullptr;
-        if (int rc = conv_scratch((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
+        if (int rc = wgrad_part_buffer((size_t)splits * (nW + a.Co) + 16, &base, st)) return rc;
         a.wg_part = base;
         a.wg_part_b = a.gb ? base + (((size_t)splits * nW + 3) & ~(size_t)3) : nullptr;
     } else if (!accumulate) {
@@ -1362,7 +1291,7 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
         return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight (folded norm): the gradient is too large for the ordered reduce");
     if (ordered) {
         float *base = nullptr;
-        if (int rc = conv_scratch((size_t)splits * (nW + Co) + 16, &base, st)) return rc;
+        if (int rc = wgrad_part_buffer((size_t)splits * (nW + Co) + 16, &base, st)) return rc;
         a.wg_part = base;
         a.wg_part_b = a.gb ? base + (((size_t)splits * nW + 3) & ~(size_t)3) : nullptr;
     } else if (!accumulate) {
@@ -1373,9 +1302,6 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
     if (ordered) return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, Co, splits, splits, accumulate ? 1 : 0, st);
     return 0;
 }
-
-int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
-                  int dil, int accumulate, hipStream_t st);   // conv.hip
 
 // The levels of a dense convolution as DcnArgs (no offsets: the regular grid is the sampling table), 32-pixel steps in *steps
 static int conv_levels(DcnArgs &a, int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
@@ -1466,8 +1392,6 @@ using namespace lsn;
 
 extern "C" {
 
-const char *lsn_last_error(void) { return lsn::err_buf(); }
-
 int lsn_debug_phase_clocks(long long *device_buf_512, int word)
 {
     constexpr int known = LSN_DBG_BLOCK_MASK | LSN_DBG_ANCHOR_ONE_WAVE | LSN_DBG_FWD_SK_ALWAYS | LSN_DBG_FWD_SK_NEVER |
@@ -1477,7 +1401,6 @@ int lsn_debug_phase_clocks(long long *device_buf_512, int word)
     lsn::g_dbg_block = word;
     return 0;
 }
-int lsn_version(void) { return 100; }
 
 // The queries: the arguments as a channels-last call binds them, then the route such a call would take
 static bool query_args(lsn::DcnArgs &a, const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
@@ -1523,16 +1446,6 @@ int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_l
     return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), true).pitched ? 1 : 0;
 }
 
-int lsn_set_math_mode(int mode)
-{
-    LSN_CHECK(mode == LSN_MATH_FP32 || mode == LSN_MATH_BF16X3 || mode == LSN_MATH_BF16X6 || mode == LSN_MATH_BF16,
-              "unknown math mode %d", mode);
-    lsn::g_math_mode = mode;
-    return 0;
-}
-
-int lsn_get_math_mode(void) { return lsn::math_mode(); }
-
 int lsn_conv2d_backward_weight_multi(int n_levels, const lsn_conv_level *levels, float *grad_w, float *grad_bias, int C,
                                      int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
                                      lsn_stream_t stream)
@@ -1549,69 +1462,6 @@ int lsn_conv2d_backward_weight(const float *x, const float *grad_out, float *gra
     lsn_conv_level L = {};
     L.x = x, L.grad_out = grad_out, L.B = B, L.H = H, L.W = W;
     return lsn_conv2d_backward_weight_multi(1, &L, grad_w, grad_bias, C, Co, kh, kw, stride, pad, dil, accumulate, stream);
-}
-
-int lsn_prof_enable(int on)
-{
-    for (auto &r : lsn::g_prof) {
-        (void)hipEventDestroy(r.e0);
-        (void)hipEventDestroy(r.e1);
-    }
-    lsn::g_prof.clear();
-    lsn::g_prof_mask = on == 1 ? ~0u : (unsigned)on;
-    return 0;
-}
-
-int lsn_prof_launch_log(int on)
-{
-    for (auto &r : lsn::g_launches) {
-        (void)hipEventDestroy(r.e0);
-        (void)hipEventDestroy(r.e1);
-    }
-    lsn::g_launches.clear();
-    lsn::g_launch_log = on != 0;
-    return 0;
-}
-
-int lsn_prof_read_launches(lsn_prof_launch *out, int max_entries)
-{
-    using namespace lsn;
-    const int n = (int)g_launches.size();
-    if (out == nullptr) return n;
-    int k = 0;
-    for (; k < n && k < max_entries; ++k) {
-        const LaunchRec &r = g_launches[k];
-        LSN_HIP(hipEventSynchronize(r.e1));
-        float ms = 0.f;
-        LSN_HIP(hipEventElapsedTime(&ms, r.e0, r.e1));
-        lsn_prof_launch &o = out[k];
-        o.kind = r.v[0], o.C = r.v[1], o.Co = r.v[2], o.kh = r.v[3], o.kw = r.v[4], o.stride = r.v[5], o.pad = r.v[6];
-        o.dil = r.v[7], o.relu = r.v[8], o.xpitch = r.v[9], o.n_levels = r.v[10], o.has_residual = r.v[11], o.has_gate = r.v[12];
-        for (int i = 0; i < 16; ++i) o.B[i] = r.B[i], o.H[i] = r.H[i], o.W[i] = r.W[i];
-        o.ms = ms;
-    }
-    return k;
-}
-
-int lsn_prof_read(lsn_prof_entry *out, int max_entries)
-{
-    using namespace lsn;
-    LSN_CHECK(out != nullptr && max_entries >= PROF_N, "lsn_prof_read needs room for %d entries", PROF_N);
-    for (int f = 0; f < PROF_N; ++f) {
-        std::memset(&out[f], 0, sizeof(out[f]));
-        std::snprintf(out[f].name, sizeof(out[f].name), "%s", kProfNames[f]);
-    }
-    for (auto &r : g_prof) {
-        LSN_HIP(hipEventSynchronize(r.e1));
-        float ms = 0.f;
-        LSN_HIP(hipEventElapsedTime(&ms, r.e0, r.e1));
-        lsn_prof_entry &e = out[r.fam];
-        e.launches += 1;
-        e.total_ms += ms;
-        e.flops += r.flops;
-        e.bytes += r.bytes;
-    }
-    return PROF_N;
 }
 
 int lsn_dcn_forward(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, const float *weight,

@@ -1,5 +1,5 @@
 // Sigmoid focal loss, NMS and the MFMA self-test of liblsnet_hip.so.
-#include "common.h"
+#include "lib_state.h"
 
 namespace lsn {
 
@@ -600,18 +600,13 @@ int lsn_sigmoid_focal_loss_backward(const float *logits, const int64_t *targets,
     return 0;
 }
 
-// library-owned scratch of the two-stage focal sums (one stream at a time, like the other scratch buffers of the library)
-static int focal_scratch(float **part_out, unsigned **ticket_out)
+// The two-stage focal sums keep their 1024 partial sums in the stream's scratch block and draw the stream's TICKET_FOCAL_SUM
+// (lib_state.h): callers on different streams share nothing.
+static int focal_partials(float **part, unsigned **ticket, hipStream_t st)
 {
-    static float *part = nullptr;
-    static unsigned *ticket = nullptr;
-    if (!part) {
-        LSN_HIP(hipMalloc(reinterpret_cast<void **>(&part), 1024 * sizeof(float) + sizeof(unsigned)));
-        lsn::lib_stat(lsn::STAT_MALLOCS, 1), lsn::lib_stat(lsn::STAT_HELD_BYTES, 1024 * sizeof(float) + sizeof(unsigned));
-        ticket = reinterpret_cast<unsigned *>(part + 1024);
-        LSN_HIP(hipMemset(ticket, 0, sizeof(unsigned)));
-    }
-    *part_out = part, *ticket_out = ticket;
+    if (int rc = lsn::stream_scratch(1024, part, st)) return rc;
+    if (int rc = lsn::lib_tickets(ticket, st)) return rc;
+    *ticket += lsn::TICKET_FOCAL_SUM;
     return 0;
 }
 
@@ -635,7 +630,7 @@ int lsn_sigmoid_focal_loss_sum(const float *logits, const int64_t *targets, cons
     }
     float *part = nullptr;
     unsigned *ticket = nullptr;
-    if (int rc = focal_scratch(&part, &ticket)) return rc;
+    if (int rc = focal_partials(&part, &ticket, stream)) return rc;
     int grid = ew_grid((size_t)N * C);
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(focal_sum_kernel, dim3(grid), dim3(256), 0, stream, logits, targets, weight, loss_sum, N, C, gamma,
@@ -666,7 +661,7 @@ int lsn_sigmoid_focal_loss_level_sums(const float *logits, const int64_t *target
     if (int rc = level_tab(t, B, N_all, L, level_starts)) return rc;
     float *part = nullptr;
     unsigned *ticket = nullptr;
-    if (int rc = focal_scratch(&part, &ticket)) return rc;
+    if (int rc = focal_partials(&part, &ticket, stream)) return rc;
     // ~16 elements per thread; coarser until the launch fits the 1024 partial sums
     for (long long per = 4096;; per *= 2) {
         int nb = 0;

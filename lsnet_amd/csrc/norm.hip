@@ -15,13 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/lsnet_hip.h"
-#include "common.h"
+#include "lib_state.h"
 #include "prof.h"
 
 namespace lsn {
-
-int lib_tickets(unsigned **p, hipStream_t st);   // conv.hip
 
 constexpr int GN_MAXLV = 16;
 constexpr int GN_PIX = 64;    // pixels per block
@@ -42,7 +39,7 @@ struct GnArgs {
     double *sums;      // [images][G][2]   shifted sum, shifted sum of squares   (zero when the statistics kernel starts)
     double *clear;     // the statistics kernel zeroes clear[0 .. nclear): the sums the PREVIOUS call of this stream left behind
     int nclear;
-    unsigned *ticket;  // self-resetting counters of this stream (conv.hip lib_tickets); [1]: the backward's image sums
+    unsigned *ticket;  // self-resetting counters of this stream (lib_state.h lib_tickets): the backward's image sums draw TICKET_GN_IMGSUM
     float *mean_rstd;  // [images][G][2]
     float *ab;         // [images][C][2]   backward: sum dy*xhat, sum dy
     float *part;       // [blocks][C][2]   backward: the same per 64-pixel block (summed per image in a fixed order)
@@ -322,7 +319,7 @@ __global__ __launch_bounds__(256) void gn_bwd_imgsum_kernel(const GnArgs a, int 
     __shared__ unsigned last;
     wait_stores();
     __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket + 1, 1u) == gridDim.x * gridDim.y - 1;
+    if (threadIdx.x == 0) last = atomicAdd(a.ticket + TICKET_GN_IMGSUM, 1u) == gridDim.x * gridDim.y - 1;
     __syncthreads();
     if (!last) return;
     for (int c = threadIdx.x; c < a.C; c += 256) {
@@ -334,7 +331,7 @@ __global__ __launch_bounds__(256) void gn_bwd_imgsum_kernel(const GnArgs a, int 
         if (a.dgamma) a.dgamma[c] = accumulate ? a.dgamma[c] + sa : sa;
         if (a.dbeta) a.dbeta[c] = accumulate ? a.dbeta[c] + sb : sb;
     }
-    if (threadIdx.x == 0) a.ticket[1] = 0;
+    if (threadIdx.x == 0) a.ticket[TICKET_GN_IMGSUM] = 0;
 }
 
 template <bool EG>
@@ -395,29 +392,17 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const GnArgs a)
 // finished).  16 memsets per training step go; calls with more than GN_SUMS_CAP sums keep the caller's workspace + memset.
 constexpr int GN_SUMS_CAP = 8192;   // doubles per buffer (images * G * 2)
 struct GnSums {
-    hipStream_t st;
     double *buf;   // [2][GN_SUMS_CAP], zeroed once
     int cur, dirty[2];
 };
-static GnSums g_gns[16];
-static int g_ngns = 0;
+static PerStream<GnSums> g_gns;
 static int gn_sums(hipStream_t st, int n, GnArgs &a)
 {
     GnSums *s = nullptr;
-    for (int i = 0; i < g_ngns; ++i)
-        if (g_gns[i].st == st) s = &g_gns[i];
-    if (!s) {
-        if (g_ngns == 16) return fail(LSN_ERR_RUNTIME, "group norm: more than 16 streams use the library");
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(LSN_ERR_RUNTIME, "group norm: first call inside a stream capture: run the step eagerly once before capturing");
-        double *np = nullptr;
-        LSN_HIP(hipMalloc(reinterpret_cast<void **>(&np), 2 * GN_SUMS_CAP * sizeof(double)));
-        lib_stat(STAT_MALLOCS, 1), lib_stat(STAT_HELD_BYTES, (long long)(2 * GN_SUMS_CAP * sizeof(double)));
-        LSN_HIP(hipMemsetAsync(np, 0, 2 * GN_SUMS_CAP * sizeof(double), st));
-        s = &g_gns[g_ngns++];
-        *s = GnSums{st, np, 0, {0, 0}};
-    }
+    auto init = [&](GnSums &g) {
+        return device_alloc(reinterpret_cast<void **>(&g.buf), 2 * GN_SUMS_CAP * sizeof(double), st, "group norm: first call", true);
+    };
+    if (int rc = g_gns.get(st, "group norm", &s, init)) return rc;
     const int cur = s->cur, oth = cur ^ 1;
     a.sums = s->buf + (size_t)cur * GN_SUMS_CAP;
     a.clear = s->buf + (size_t)oth * GN_SUMS_CAP;
@@ -692,9 +677,7 @@ int lsn_group_norm_forward(int n_levels, const lsn_gn_level *levels, int C, int 
     // of the other it clears.  A captured graph replays the capture-time choice, which is right only while replays and eager
     // calls keep the parity the capture saw; a capturing stream therefore takes the self-contained form: the caller's
     // workspace and a memset node.)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    if (images * G * 2 <= GN_SUMS_CAP && !capturing) {
+    if (images * G * 2 <= GN_SUMS_CAP && !stream_capturing(st)) {
         if (int rc = gn_sums(st, images * G * 2, a)) return rc;
     } else {
         a.sums = reinterpret_cast<double *>(workspace);

@@ -1,6 +1,6 @@
 // Per-kernel-family launch timing (lsn_prof_*): HIP events recorded on the launch stream around each launch of a
 // family, so bench.py can quote every family's own average duration, algorithmic flops and bytes live and put the
-// roofline on whichever family dominates the step.  State lives in dcn.hip.
+// roofline on whichever family dominates the step.  State and the lsn_prof_* accessors live in lib_state.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
