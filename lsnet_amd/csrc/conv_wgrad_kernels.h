@@ -519,10 +519,16 @@ __device__ __forceinline__ void wgrad_reduce_bn_body(const float *__restrict__ p
             const float4 wv = reinterpret_cast<const float4 *>(f.w)[e];
             dot += (wv.x * s.x + wv.y * s.y) + (wv.z * s.z + wv.w * s.w);
             float4 *d = reinterpret_cast<float4 *>(gw) + e;
-            float4 o = make_float4(ac * s.x, ac * s.y, ac * s.z, ac * s.w);
+            // gw += a G as ONE fma per element, spelled out: left to the compiler, the multi-job kernel of a deferred flush
+            // (`accumulate` a constant there) contracts a * G + gw while the immediate reduce below rounds the product first --
+            // other bits onto a non-zero gradient than the header promises (lsn_wgrad_defer)
+            float4 o;
             if (accumulate) {
                 const float4 q = *d;
-                o.x += q.x, o.y += q.y, o.z += q.z, o.w += q.w;
+                o = make_float4(__builtin_fmaf(ac, s.x, q.x), __builtin_fmaf(ac, s.y, q.y), __builtin_fmaf(ac, s.z, q.z),
+                                __builtin_fmaf(ac, s.w, q.w));
+            } else {
+                o = make_float4(ac * s.x, ac * s.y, ac * s.z, ac * s.w);
             }
             *d = o;
         }
@@ -535,9 +541,9 @@ __device__ __forceinline__ void wgrad_reduce_bn_body(const float *__restrict__ p
     if (tid == 0) {
         const float d4 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
         const float b4 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        const float dg = (d4 - f.mean[co] * b4) * rstd;
+        const float t = d4 - f.mean[co] * b4;
         f.dbeta[co] = accumulate ? f.dbeta[co] + b4 : b4;
-        f.dgamma[co] = accumulate ? f.dgamma[co] + dg : dg;
+        f.dgamma[co] = accumulate ? __builtin_fmaf(t, rstd, f.dgamma[co]) : t * rstd;   // (one fma as well, in both kernels)
     }
 }
 
