@@ -169,6 +169,17 @@ int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_l
  * backward's column-gradient GEMM), i.e. when shape->weights_prepared may be set; workspace / gather_workspace as they will
  * be passed. */
 int lsn_dcn_prepared_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward);
+/* (tests) The anchor lists of lsn_dcn_backward's atomic-free grad_input path for this call, and nothing else of it: routed and
+ * planned as the call would be (shape->workspace / gather_workspace as they would be passed; the lists are built in
+ * gather_workspace).  A SAMPLE is (pixel of the launch, deformable group, tap), id = pixel * dg*kh*kw + group * kh*kw + tap with
+ * the levels' pixels in level order; its ANCHOR is the floor of its position on the (B, H + 1, W + 1) grid of the grad_input
+ * buffer it scatters into, numbered launch-wide.  counts (host) receives {samples, anchors}.  Device outputs, all three or --
+ * to ask for the counts only -- none: sample_anchor[samples], the anchor of every sample, -1 for a sample on no list (outside
+ * the map, or a level without grad_input); list_start[anchors + 1], the exclusive list offsets; list_sample[samples], the
+ * sample ids of the lists back to back, each list ascending, -1 behind the last.  LSN_ERR_UNSUPPORTED for a call that
+ * lsn_dcn_backward serves without lists, and for LSN_NCHW (that entry routes on temporaries of its own). */
+int lsn_dcn_anchor_lists(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, lsn_layout layout,
+                         int *sample_anchor, int *list_start, int *list_sample, int64_t *counts, lsn_stream_t stream);
 
 /* ---- one-to-one replacements of the reference extension's functions ----------------------- */
 /* Each takes contiguous NCHW tensors like the reference and the same scalar arguments in the

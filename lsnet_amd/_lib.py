@@ -154,6 +154,7 @@ def _signatures():
         'lsn_dcn_backward_workspace_bytes': (q, [P(DcnShape), i, P(DcnLevel)]),
         'lsn_dcn_pitched_ok': (i, [P(DcnShape), i, P(DcnLevel), i]),
         'lsn_dcn_prepared_ok': (i, [P(DcnShape), i, P(DcnLevel), i]),
+        'lsn_dcn_anchor_lists': (i, [P(DcnShape), i, P(DcnLevel), i, p, p, p, p, p]),
         'lsn_deform_conv_forward': (i, [p] * 4 + [i] * 16 + [p]),
         'lsn_deform_conv_backward_input': (i, [p] * 6 + [i] * 16 + [p]),
         'lsn_deform_conv_backward_parameters': (i, [p] * 4 + [i] * 15 + [f, i, p]),

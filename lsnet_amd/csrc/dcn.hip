@@ -6,8 +6,6 @@
 
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "dcn_kernels.h"
 #include "dcn_mm_kernels.h"
 #include "dcn_grouped_kernels.h"
@@ -443,13 +441,12 @@ static bool bwd_grouped_ok(const DcnArgs &a)
     return bwd_offsets_ok(a);
 }
 
-// ---- atomic-free grad_input: workspace plan of the bin / scan / fill / sort / gather sequence (dcn_gather_kernels.h) ----
+// ---- atomic-free grad_input: workspace plan of the list sort / gather sequence (dcn_gather_kernels.h) ----
 struct GatherPlan {
     bool ok = false;
     int nsamples = 0, nanchors = 0;
-    size_t scan_tmp = 0;
-    size_t o_gcol = 0, o_cnt = 0, o_start = 0, o_anchor = 0, o_rank = 0, o_frac = 0, o_ent = 0, o_tmp = 0, o_gtap = 0, bytes = 0;
-    size_t o_S = 0, o_H = 0, o_ent2 = 0;
+    size_t o_gcol = 0, o_hist = 0, o_start = 0, o_key = 0, o_ent = 0, o_gtap = 0, bytes = 0;
+    size_t o_S = 0, o_H = 0, o_pairs = 0;
     GatherArgs ga;        // groups gathered per 4x4 pixel block
     AnchorArgs aa;        // groups with long lists: gathered per anchor (dcn_anchor_sum / combine)
     int anchor_pixels = 0;
@@ -498,6 +495,7 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl, bool all_anchor)
     if (a.C % 4 != 0 || (a.C / a.dg) % 4 != 0) return;
     pl.nsamples = (int)(prow * KD);
     pl.nanchors = (int)anchors;
+    if (ds_digit_bits(pl.nanchors) > DS_MAX_DIGIT_BITS) return;   // (cannot happen below 2^30 anchors: the LDS of the list sort)
     // Groups with more than ~400 samples per 4x4 pixel block go to the per-anchor gather (the pyramid op's coarse source
     // levels); the others keep the block walk.
     constexpr int anchor_thr = 400;
@@ -546,20 +544,14 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl, bool all_anchor)
     ga.NB = (int)Q;
     ga.C = a.C, ga.K = K, ga.KD = KD, ga.dg = a.dg;
     aa.C = a.C, aa.K = K, aa.KD = KD, aa.dg = a.dg;
-    size_t tmp = 0;
-    if (rocprim::exclusive_scan((void *)nullptr, tmp, (int *)nullptr, (int *)nullptr, 0, (size_t)pl.nanchors + 1,
-                                rocprim::plus<int>(), (hipStream_t)0) != hipSuccess)
-        return;
-    pl.scan_tmp = tmp;
     size_t o = 0;
     pl.o_gcol = o, o = align256(o + (size_t)prow * K * a.C * sizeof(float));
-    pl.o_cnt = o, o = align256(o + ((size_t)pl.nanchors + 1) * sizeof(int));
+    // the histogram of one pass, [digit][block] + the digits' totals: (blocks + 1) x 2^db ints with 2^db <= 2 sqrt(anchors),
+    // i.e. at most 4 bytes per sample + 16 sqrt(anchors) -- less than the anchor counters and sample ranks it replaces
+    pl.o_hist = o, o = align256(o + ds_hist_ints(pl.nsamples, pl.nanchors) * sizeof(int));
     pl.o_start = o, o = align256(o + ((size_t)pl.nanchors + 1) * sizeof(int));
-    pl.o_anchor = o, o = align256(o + (size_t)pl.nsamples * sizeof(int));
-    pl.o_rank = o, o = align256(o + (size_t)pl.nsamples * sizeof(int));
-    pl.o_frac = o, o = align256(o + (size_t)pl.nsamples * sizeof(float2));
+    pl.o_key = o, o = align256(o + (size_t)pl.nsamples * sizeof(int));
     pl.o_ent = o, o = align256(o + (size_t)pl.nsamples * sizeof(GEntry));
-    pl.o_tmp = o, o = align256(o + tmp + 256);
     pl.o_gtap = o, o = align256(o + ((size_t)pl.nsamples + 1) * sizeof(Tap));   // + the all-zero entry
     pl.o_S = o, o = align256(o + (size_t)pl.aa.NA * 4 * a.C * sizeof(float));
     // corner sums (dcn_offgrad_kernel): one slot per 256-channel block where the per-anchor sums split them over blockIdx.y
@@ -570,7 +562,7 @@ static void gather_plan(DcnArgs &a, GatherPlan &pl, bool all_anchor)
     aa.ncb = dbg_on(LSN_DBG_ANCHOR_ONE_WAVE) ? 1 : ncb_max;
     aa.hb_slot = (long long)pl.nsamples * 4;
     pl.o_H = o, o = align256(o + (size_t)pl.nsamples * 4 * sizeof(float) * ncb_max);
-    pl.o_ent2 = o, o = align256(o + (size_t)pl.nsamples * sizeof(GEntry));   // ordering of the lists above 64 entries
+    pl.o_pairs = o, o = align256(o + (size_t)pl.nsamples * 2 * sizeof(int2));   // the (key, sample) pairs of the sort, ping and pong
     pl.bytes = o;
     pl.ok = true;
 }
@@ -744,9 +736,9 @@ static int bwd_tap_groups(const DcnArgs &a)
     return best;
 }
 
-// A second stream per launch stream for the list building of the backward-data path.  bin -> scan -> fill -> sort are
-// latency-bound kernels of a few thousand short workgroups (50 - 60 us each on the tower launch, 0.1 - 0.2 of the chip's
-// wave slots busy) that depend on the offsets only; the column-gradient GEMM beside them depends on grad_output only and
+// A second stream per launch stream for the list building of the backward-data path.  The kernels of the list sort
+// (build_lists) are short, latency-bound launches of a few hundred workgroups that depend on the offsets only; the
+// column-gradient GEMM beside them depends on grad_output only and
 // leaves ~100 VGPRs per SIMD and 110 KB of LDS per CU free.  Fork after the workspace is known, join before the
 // per-anchor sums.  (Not the same experiment as the weight gradients on a side stream, profiles/r4_side_stream.txt: two
 // MFMA kernels take the matrix pipe from each other; these kernels wait on memory while the GEMM computes.)
@@ -776,16 +768,50 @@ static int side_stream(hipStream_t st, SideStream **out)
 // and ran the per-anchor sums of band i on the side stream beside the GEMM of band i + 1, the column gradients of a band
 // still in the Infinity Cache: tower +7 % slower, pyramid unchanged, profiles/r5_band_pipeline.txt.  GEMM and sums are both
 // bound by the memory system; removed.)
+// The sampling table (a.gtap, a.gtap_rows) and the anchor lists of a launch -- start[anchors + 1], ent[] -- on stream `st`:
+// keys + low-digit histogram, then per pass scan and stable scatter (dcn_gather_kernels.h, dcn_sort_plan.h), then the list
+// offsets.  Seven launches for up to 2^22 anchors (two passes), ten above; no memset, no blocking call.
+static int build_lists(DcnArgs &a, const GatherPlan &pl, unsigned char *ws, hipStream_t st)
+{
+    int *hist = reinterpret_cast<int *>(ws + pl.o_hist), *start = reinterpret_cast<int *>(ws + pl.o_start);
+    int *key = reinterpret_cast<int *>(ws + pl.o_key);
+    int2 *pairs[2] = {reinterpret_cast<int2 *>(ws + pl.o_pairs), reinterpret_cast<int2 *>(ws + pl.o_pairs) + pl.nsamples};
+    GEntry *ent = reinterpret_cast<GEntry *>(ws + pl.o_ent);
+    Tap *gtap = reinterpret_cast<Tap *>(ws + pl.o_gtap);   // also read by the column-gradient kernels and by the weight-gradient pass
+    const int KD = a.kh * a.kw * a.dg, n = pl.nsamples, na = pl.nanchors;
+    a.gtap_rows = n / KD;
+    const int db = ds_digit_bits(na), passes = ds_passes(na), nblocks = ds_blocks(n);
+    const dim3 grid(nblocks), block(DS_THREADS), kblock(DS_KEY_THREADS);
+    const size_t lds = ds_scatter_lds_bytes(db);   // (<= 40 KB: gather_plan)
+    hipLaunchKernelGGL(dcn_list_keys_kernel, grid, kblock, 0, st, a, n, na, db, nblocks, key, hist, gtap);
+    a.gtap = gtap;
+    for (int p = 0; p < passes; ++p) {
+        const int2 *in = p > 0 ? pairs[(p - 1) & 1] : nullptr;
+        int2 *out = pairs[p & 1];
+        if (p > 0) hipLaunchKernelGGL(dcn_list_hist_kernel, grid, kblock, 0, st, n, p, db, nblocks, in, hist);
+        hipLaunchKernelGGL(dcn_list_scan_kernel, dim3(1 << db), block, 0, st, hist, db, nblocks);
+        if (p == 0)
+            hipLaunchKernelGGL((dcn_list_scatter_kernel<true, false>), grid, block, lds, st, n, na, p, db, nblocks, hist, key, in, out,
+                               ent, (int *)nullptr, gtap, KD, a.gtap_rows);
+        else if (p + 1 < passes)
+            hipLaunchKernelGGL((dcn_list_scatter_kernel<false, false>), grid, block, lds, st, n, na, p, db, nblocks, hist, key, in, out,
+                               ent, (int *)nullptr, gtap, KD, a.gtap_rows);
+        else   // the last pass: entries, and the sorted keys where its pairs would have gone
+            hipLaunchKernelGGL((dcn_list_scatter_kernel<false, true>), grid, block, lds, st, n, na, p, db, nblocks, hist, key, in,
+                               (int2 *)nullptr, ent, reinterpret_cast<int *>(out), gtap, KD, a.gtap_rows);
+    }
+    const int *skey = reinterpret_cast<const int *>(pairs[(passes - 1) & 1]);
+    hipLaunchKernelGGL(dcn_list_starts_kernel, dim3(cdiv(na + 1, 256)), dim3(256), 0, st, n, na, skey, start);
+    LSN_HIP(hipGetLastError());
+    return 0;
+}
+
 static int launch_bwd_gather(DcnArgs &a, DcnRoute &r, unsigned char *ws, hipStream_t st_main)
 {
     GatherPlan &pl = r.plan;
     a.gcol = reinterpret_cast<float *>(ws + pl.o_gcol);
-    int *cnt = reinterpret_cast<int *>(ws + pl.o_cnt), *start = reinterpret_cast<int *>(ws + pl.o_start);
-    int *sanchor = reinterpret_cast<int *>(ws + pl.o_anchor), *srank = reinterpret_cast<int *>(ws + pl.o_rank);
-    float2 *sfrac = reinterpret_cast<float2 *>(ws + pl.o_frac);
+    int *start = reinterpret_cast<int *>(ws + pl.o_start);
     GEntry *ent = reinterpret_cast<GEntry *>(ws + pl.o_ent);
-    Tap *gtap = reinterpret_cast<Tap *>(ws + pl.o_gtap);   // also read by the GEMM below and by the weight-gradient pass
-    a.gtap_rows = pl.nsamples / (a.kh * a.kw * a.dg);
     // lists on the side stream only beside the dense GEMM (the other column-gradient kernels read the tap table)
     SideStream *side = nullptr;
     if (r.data == GATHER_MM)
@@ -795,18 +821,7 @@ static int launch_bwd_gather(DcnArgs &a, DcnRoute &r, unsigned char *ws, hipStre
         LSN_HIP(hipEventRecord(side->fork, st_main));
         LSN_HIP(hipStreamWaitEvent(side->side, side->fork, 0));
     }
-    LSN_HIP(hipMemsetAsync(cnt, 0, ((size_t)pl.nanchors + 1) * sizeof(int), st));
-    hipLaunchKernelGGL(dcn_bin_kernel, dim3(cdiv(pl.nsamples, 256)), dim3(256), 0, st, a, pl.nsamples, cnt, sanchor, srank, sfrac,
-                       gtap);
-    a.gtap = gtap;
-    size_t tmp = pl.scan_tmp;
-    LSN_HIP(rocprim::exclusive_scan(ws + pl.o_tmp, tmp, cnt, start, 0, (size_t)pl.nanchors + 1, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(dcn_fill_kernel, dim3(cdiv(pl.nsamples, 256)), dim3(256), 0, st, pl.nsamples, start, sanchor, srank, sfrac,
-                       ent, gtap, a.kh * a.kw * a.dg, a.gtap_rows);
-    int sort_blocks = cdiv(pl.nanchors, 4);
-    if (sort_blocks > 4096) sort_blocks = 4096;
-    hipLaunchKernelGGL(dcn_sort_lists_kernel, dim3(sort_blocks), dim3(256), 0, st, pl.nanchors, start, ent,
-                       reinterpret_cast<GEntry *>(ws + pl.o_ent2));
+    if (int rc = build_lists(a, pl, ws, st)) return rc;
     if (side) {
         LSN_HIP(hipEventRecord(side->join, side->side));
         st = st_main;
@@ -1444,6 +1459,42 @@ int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_l
     if (!query_args(a, shape, n_levels, levels, backward)) return 0;
     if (!backward) return route_forward(a, *shape, LSN_NHWC).pitched ? 1 : 0;
     return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), true).pitched ? 1 : 0;
+}
+
+// (tests) the anchor lists lsn_dcn_backward would build for this call, and nothing else of it
+int lsn_dcn_anchor_lists(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, lsn_layout layout,
+                         int *sample_anchor, int *list_start, int *list_sample, int64_t *counts, lsn_stream_t stream)
+{
+    using namespace lsn;
+    if (!shape || !levels || !counts) return fail(LSN_ERR_INVALID, "shape/levels/counts is NULL");
+    const lsn_dcn_shape &s = *shape;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = check_shape(s)) return rc;
+    DcnArgs a;
+    // (the reference-layout entry points route on temporaries of their own, which this entry does not make)
+    if (layout != LSN_NHWC) return fail(LSN_ERR_UNSUPPORTED, "lsn_dcn_anchor_lists: LSN_NHWC only");
+    if (int rc = fill_levels(a, s, n_levels, levels, BWD_BM)) return rc;
+    for (int i = 0; i < n_levels; ++i) {
+        LSN_CHECK(levels[i].input && levels[i].grad_output, "level %d: input/grad_output is NULL", i);
+        a.lv[i].x = levels[i].input;
+        a.lv[i].gout = levels[i].grad_output;
+        a.lv[i].gx = levels[i].grad_input;
+    }
+    void *gws = s.gather_workspace;
+    DcnRoute r = route_backward(a, s, layout, gws, gather_ws_bytes(s), false);
+    if (!r.gather()) return fail(LSN_ERR_UNSUPPORTED, "lsn_dcn_anchor_lists: this call builds no anchor lists (route without the gather pass)");
+    const GatherPlan &pl = r.plan;
+    counts[0] = pl.nsamples, counts[1] = pl.nanchors;
+    if (!sample_anchor && !list_start && !list_sample) return 0;   // the sizes only
+    LSN_CHECK(sample_anchor && list_start && list_sample, "lsn_dcn_anchor_lists: all three outputs or none");
+    unsigned char *w = reinterpret_cast<unsigned char *>(gws);
+    if (int rc = build_lists(a, pl, w, st)) return rc;
+    const int n = pl.nsamples > pl.nanchors + 1 ? pl.nsamples : pl.nanchors + 1;
+    hipLaunchKernelGGL(dcn_list_export_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, pl.nsamples, pl.nanchors,
+                       reinterpret_cast<const int *>(w + pl.o_key), reinterpret_cast<const int *>(w + pl.o_start),
+                       reinterpret_cast<const GEntry *>(w + pl.o_ent), sample_anchor, list_start, list_sample);
+    LSN_HIP(hipGetLastError());
+    return 0;
 }
 
 int lsn_conv2d_backward_weight_multi(int n_levels, const lsn_conv_level *levels, float *grad_w, float *grad_bias, int C,

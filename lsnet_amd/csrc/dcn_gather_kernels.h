@@ -1,9 +1,10 @@
 // Atomic-free backward-data of the deformable family (included by dcn_kernels.h, which holds DcnArgs / Tap / Lvl): anchor
-// lists (bin / scan / fill / sort), per-anchor corner sums, the four-anchor combine, offset / mask gradients from the
-// corner dot products, and the fmaf-chain column gradients of grouped calls.  This is the DEFAULT path of every math mode;
-// what is left in dcn_kernels.h are the general-shape kernels (channel counts the kernels of dcn_mm_kernels.h do not
-// take, callers without the gather workspace) and the exact-mode GEMMs.
+// lists (a stable radix sort of the samples by anchor: dcn_list_*_kernel), per-anchor corner sums, the four-anchor combine,
+// offset / mask gradients from the corner dot products, and the fmaf-chain column gradients of grouped calls.  This is the
+// DEFAULT path of every math mode; what is left in dcn_kernels.h are the general-shape kernels (channel counts the kernels
+// of dcn_mm_kernels.h do not take, callers without the gather workspace) and the exact-mode GEMMs.
 #pragma once
+#include "dcn_sort_plan.h"
 
 namespace lsn {
 
@@ -14,10 +15,14 @@ namespace lsn {
 // ANCHOR (y0, x0) = floor(py, px), y0 in [-1, H-1], x0 in [-1, W-1].  Input pixel q = (y, x) therefore receives
 //   from anchor (y, x)     the (1-ly)(1-lx) corner,   from (y, x-1)   the (1-ly) lx corner,
 //   from anchor (y-1, x)   the ly (1-lx) corner,      from (y-1, x-1) the ly lx corner
-// of every sample anchored there.  dcn_bin_kernel counts the samples of every anchor (integer atomics, 1 per sample
-// against 4 x C float atomics per sample before) and records each sample's rank; a single-block scan turns the counts
-// into list offsets; dcn_fill_kernel writes {sample, ly, lx} entries; dcn_sort_lists_kernel orders each list by sample
-// id (so that the summation order is fixed); dcn_gather_kernel walks the four lists of every input pixel, reads the
+// of every sample anchored there.  The lists -- per anchor, {sample, ly, lx} entries in ascending sample id, so that the
+// summation order is fixed -- are a STABLE SORT of the samples by anchor id (dcn_sort_plan.h): the samples are enumerated
+// in ascending id, so a stable sort leaves every list ordered by construction, with no global atomic, no per-list sort and
+// no counter to zero.  dcn_list_keys_kernel builds the sampling table and every sample's key (its anchor, or the sentinel
+// `nanchors` for a sample outside the map or of a level without grad_input) with the histogram of the low digit;
+// dcn_list_scan_kernel turns a histogram into offsets; dcn_list_scatter_kernel moves (key, sample) pairs to their places,
+// the last pass writing the entries themselves; dcn_list_hist_kernel counts the next digit; dcn_list_starts_kernel finds
+// every list's first entry in the sorted keys.  dcn_gather_kernel walks the four lists of every input pixel, reads the
 // mask-weighted column-gradient rows (C contiguous floats each) and writes grad_input once.
 // Levels that scatter into the same grad_input buffer (the pyramid op: one source map for several destination
 // levels) share one anchor grid, so their contributions are summed here instead of by separate tensor adds.
@@ -145,94 +150,268 @@ __global__ __launch_bounds__(256) void dcn_gcol_grouped_kernel(const DcnArgs a, 
     }
 }
 
-// one thread per sample: anchor, rank inside the anchor's list, fractions
-// (Walking the samples tap-major like the table -- coalesced 32-byte stores, the integer atomics of a wave spread over 64
-// neighbouring anchors -- measured no difference in the round-4 A/B: 604.9 vs 607.0 us per tower backward.)
-__global__ void dcn_bin_kernel(const DcnArgs a, int nsamples, int *__restrict__ cnt, int *__restrict__ sanchor,
-                               int *__restrict__ srank, float2 *__restrict__ sfrac, Tap *__restrict__ gtap)
+// ---- the anchor lists: a stable least-significant-digit radix sort of (anchor key, sample id), dcn_sort_plan.h ----
+// A pass = histogram (of the first pass: in dcn_list_keys_kernel) -> dcn_list_scan_kernel -> dcn_list_scatter_kernel, all
+// three cut into the same blocks of DS_BLOCK consecutive elements.  No global atomic, no zero fill: every histogram cell and
+// every output element is written exactly once.  The only atomics are integer adds in LDS (histograms: a sum of ones in any
+// order), so keys, offsets and lists are the same bits on every run.
+
+// One workgroup per block of DS_BLOCK consecutive samples: the sampling table entry of every sample, its key, and the block's
+// histogram of the low digit.  DS_KEY_THREADS = 1024 threads with DS_BLOCK / 1024 = 2 samples each: the kernel is a chain of
+// dependent loads per sample (offsets and modulation scalar -> table entry -> key), so what it needs is samples in flight --
+// both samples' loads are issued before either is used, and a launch has one thread per two samples however few workgroups
+// it has (the tower-sized call: 197; a backbone layer of 8 400 pixels: 37).  With 256 threads walking 8 samples each in
+// sequence the kernel took 65 us on the tower-sized call against 37 us of the one-sample-per-thread kernel it replaced.
+__global__ __launch_bounds__(DS_KEY_THREADS) void dcn_list_keys_kernel(const DcnArgs a, int nsamples, int nanchors, int db, int nblocks,
+                                                                       int *__restrict__ key, int *__restrict__ hist,
+                                                                       Tap *__restrict__ gtap)
 {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;   // sample id (prow * KD + kd)
-    if (s >= nsamples) return;
+    constexpr int PER = DS_BLOCK / DS_KEY_THREADS;
+    __shared__ int h[DS_MAX_DIGITS];
+    const int ndig = 1 << db;
+    for (int d = threadIdx.x; d < ndig; d += DS_KEY_THREADS) h[d] = 0;
+    __syncthreads();
     const int K = a.kh * a.kw, KD = K * a.dg;
-    const int prow = s / KD, kd = s - prow * KD;
-    const int dgi = kd / K, k = kd - dgi * K;
-    const Lvl &L = find_level_by_row(a, prow);
-    int anchor = -1, rank = 0;
-    float2 fr = make_float2(0.f, 0.f);
-    int4 yx = make_int4(0, 0, 0, 0);
-    const Tap t = make_tap_ex(a, L, prow - L.prow0, k, dgi, &yx);
-    gtap[(size_t)kd * a.gtap_rows + prow] = t;   // k-major: a 32-pixel step of one tap is 1 KB contiguous
-    if (s == 0) {
-        Tap z = {};
-        gtap[(size_t)KD * a.gtap_rows] = z;   // the "no sample" entry behind the table
+    const Lvl *lv[PER];
+    TapRaw raw[PER];
+    int prow[PER], kd[PER];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {   // the loads of all samples of the thread
+        const int s = blockIdx.x * DS_BLOCK + r * DS_KEY_THREADS + threadIdx.x;   // sample id (prow * KD + kd)
+        const int sc = s < nsamples ? s : nsamples - 1;
+        prow[r] = sc / KD, kd[r] = sc - prow[r] * KD;
+        const int dgi = kd[r] / K;
+        lv[r] = &find_level_by_row(a, prow[r]);
+        raw[r] = tap_raw(a, *lv[r], prow[r] - lv[r]->prow0, kd[r] - dgi * K, dgi);
     }
-    if (L.gx != nullptr && t.flags) {
-        const int y0 = (t.flags & 3) ? yx.x : -1, x0 = (t.flags & 5) ? yx.y : -1;   // unclamped floor(py), floor(px)
-        const int HWo = L.Ho * L.Wo;
-        const int b = (prow - L.prow0) / HWo;
-        anchor = L.abase + (b * (L.H + 1) + y0 + 1) * (L.W + 1) + x0 + 1;
-        rank = atomicAdd(&cnt[anchor], 1);
-        fr = make_float2(t.ly, t.lx);
-    }
-    sanchor[s] = anchor;
-    srank[s] = rank;
-    sfrac[s] = fr;
-}
-
-__global__ void dcn_fill_kernel(int nsamples, const int *__restrict__ start, const int *__restrict__ sanchor,
-                                const int *__restrict__ srank, const float2 *__restrict__ sfrac, GEntry *__restrict__ ent,
-                                const Tap *__restrict__ gtap, int KD, int gtap_rows)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nsamples) return;
-    const int an = sanchor[s];
-    if (an < 0) return;
-    GEntry e;
-    const int prow = s / KD, kd = s - prow * KD;
-    e.s = s, e.pad = __float_as_int(gtap[(size_t)kd * gtap_rows + prow].m);   // the sample's modulation scalar
-    const float2 f = sfrac[s];
-    e.ly = f.x, e.lx = f.y;
-    ent[start[an] + srank[s]] = e;
-}
-
-// one wave per anchor list: every list is rewritten in ascending sample order (the arrival order is that of the integer
-// atomics of dcn_bin_kernel: different on every run).  Up to 64 entries: ranks by 64 lane reads.  Longer lists (hundreds of
-// samples converging on one landmark in the pyramid op): a lane ranks its every-64th entries against the whole list, 64
-// keys at a time, writes them in order to `tmp` and the wave copies the range back -- n^2 / 64 compares per lane, ~10 us
-// for 700 entries.  tmp == NULL: long lists keep their arrival order (round 2's behaviour).
-__global__ __launch_bounds__(256) void dcn_sort_lists_kernel(int nanchors, const int *__restrict__ start, GEntry *__restrict__ ent,
-                                                             GEntry *__restrict__ tmp)
-{
-    const int lane = threadIdx.x & 63;
-    const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int an = wid; an < nanchors; an += nw) {
-        const int b = start[an], n = start[an + 1] - b;
-        if (n < 2) continue;
-        if (n > 64) {
-            if (tmp == nullptr) continue;
-            for (int i0 = 0; i0 < n; i0 += 64) {          // this lane's entry i0 + lane
-                const bool mine = i0 + lane < n;
-                GEntry e = {};
-                if (mine) e = ent[b + i0 + lane];
-                int rank = 0;
-                for (int j0 = 0; j0 < n; j0 += 64) {      // against keys j0 .. j0 + 63
-                    const int kj = j0 + lane < n ? ent[b + j0 + lane].s : 0x7fffffff;
-                    const int m = min(64, n - j0);
-                    for (int j = 0; j < m; ++j) rank += (__builtin_amdgcn_readlane(kj, j) < e.s) ? 1 : 0;
-                }
-                if (mine) tmp[b + rank] = e;
-            }
-            __threadfence();
-            for (int i = lane; i < n; i += 64) ent[b + i] = tmp[b + i];
-            continue;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int s = blockIdx.x * DS_BLOCK + r * DS_KEY_THREADS + threadIdx.x;
+        if (s >= nsamples) continue;
+        const Lvl &L = *lv[r];
+        const int dgi = kd[r] / K, k = kd[r] - dgi * K;
+        int4 yx = make_int4(0, 0, 0, 0);
+        const Tap t = tap_finish(a, L, prow[r] - L.prow0, k, raw[r], &yx);
+        gtap[(size_t)kd[r] * a.gtap_rows + prow[r]] = t;   // k-major: a 32-pixel step of one tap is 1 KB contiguous
+        if (s == 0) {
+            Tap z = {};
+            gtap[(size_t)KD * a.gtap_rows] = z;   // the "no sample" entry behind the table
         }
-        GEntry e = {};
-        if (lane < n) e = ent[b + lane];
-        const int key = lane < n ? e.s : 0x7fffffff;
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += (__builtin_amdgcn_readlane(key, j) < key) ? 1 : 0;   // sample ids are distinct
-        if (lane < n) ent[b + rank] = e;
+        int anchor = nanchors;   // the sentinel: no list
+        if (L.gx != nullptr && t.flags) {
+            const int y0 = (t.flags & 3) ? yx.x : -1, x0 = (t.flags & 5) ? yx.y : -1;   // unclamped floor(py), floor(px)
+            const int HWo = L.Ho * L.Wo;
+            const int b = (prow[r] - L.prow0) / HWo;
+            anchor = L.abase + (b * (L.H + 1) + y0 + 1) * (L.W + 1) + x0 + 1;
+        }
+        key[s] = anchor;
+        atomicAdd(&h[ds_digit(anchor, 0, db)], 1);
     }
+    __syncthreads();
+    for (int d = threadIdx.x; d < ndig; d += DS_KEY_THREADS) hist[ds_hist_at(d, blockIdx.x, nblocks)] = h[d];
+}
+
+// histogram of digit `pass` (>= 1) of the pairs the previous pass left (DS_KEY_THREADS threads, two pairs each, as above)
+__global__ __launch_bounds__(DS_KEY_THREADS) void dcn_list_hist_kernel(int nsamples, int pass, int db, int nblocks,
+                                                                       const int2 *__restrict__ in, int *__restrict__ hist)
+{
+    constexpr int PER = DS_BLOCK / DS_KEY_THREADS;
+    __shared__ int h[DS_MAX_DIGITS];
+    const int ndig = 1 << db;
+    for (int d = threadIdx.x; d < ndig; d += DS_KEY_THREADS) h[d] = 0;
+    __syncthreads();
+    int kk[PER];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int i = blockIdx.x * DS_BLOCK + r * DS_KEY_THREADS + threadIdx.x;
+        kk[r] = i < nsamples ? in[i].x : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < PER; ++r)
+        if (blockIdx.x * DS_BLOCK + r * DS_KEY_THREADS + threadIdx.x < nsamples) atomicAdd(&h[ds_digit(kk[r], pass, db)], 1);
+    __syncthreads();
+    for (int d = threadIdx.x; d < ndig; d += DS_KEY_THREADS) hist[ds_hist_at(d, blockIdx.x, nblocks)] = h[d];
+}
+
+// exclusive sum over the 256 threads of a workgroup (wave scans, the four wave totals through `wsum`); *total: the sum of all
+__device__ __forceinline__ int block_exclusive_sum(int v, int *wsum, int *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < DS_WAVES; ++w) {
+        const int t = wsum[w];
+        before += w < wave ? t : 0;
+        all += t;
+    }
+    __syncthreads();   // wsum may be written again
+    *total = all;
+    return before + x - v;
+}
+
+// One workgroup per digit: its row of the histogram ([digit][block]) becomes, in place, the exclusive sum over the blocks;
+// the row's total goes behind the histogram.  (The sum over the smaller digits is formed by the scatter kernel from those
+// totals: 2^db values, against a scan of 2^db x blocks values by a single workgroup here.)
+__global__ __launch_bounds__(DS_THREADS) void dcn_list_scan_kernel(int *__restrict__ hist, int db, int nblocks)
+{
+    __shared__ int wsum[DS_WAVES];
+    int *row = hist + ds_hist_at(blockIdx.x, 0, nblocks);
+    int carry = 0;
+    for (int base = 0; base < nblocks; base += DS_THREADS) {
+        const int i = base + threadIdx.x;
+        const int v = i < nblocks ? row[i] : 0;
+        int total;
+        const int ex = block_exclusive_sum(v, wsum, &total);
+        if (i < nblocks) row[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) hist[ds_hist_at(1 << db, 0, nblocks) + blockIdx.x] = carry;
+}
+
+// The stable scatter of one pass.  A wave walks its DS_ROWS rows of 64 elements in order.  Per row the lanes that hold the
+// same digit are found with db ballots; a lane's rank in its row is the popcount of that mask below it, and the digit's count
+// in the wave's earlier rows is read from the wave's own slice of LDS, which the first lane of every digit then advances --
+// one read and one write instruction per row, in program order, no atomics.  After a barrier the four waves' counts are
+// prefixed in wave order on top of the scanned histogram, and every element goes to ds_position(...).
+// FIRST: the input is key[s], the sample id its index.  LAST: the output is the list entry itself -- {s, bits of the
+// modulation scalar, ly, lx} from the sampling table -- and the sorted key (for dcn_list_starts_kernel); sentinel samples
+// leave no entry.  Every store is guarded by pos < nsamples.
+// Dynamic LDS, ds_scatter_lds_bytes(db): the DS_WAVES count slices and the scanned bases, 2^db ints each (5 KB at the
+// benchmark's 8-bit digits, 40 KB at the widest, 11 bits).  Every workgroup forms the prefix over the 2^db digit totals for
+// itself -- 2^db contiguous ints from L2 and one block scan, against one more launch to store it -- and reads its own column
+// of the scanned histogram (2^db ints, a block apart).  The element loads are issued first, so that they are in flight under
+// that prologue and not one row at a time between the ballots.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(DS_THREADS) void dcn_list_scatter_kernel(int nsamples, int nanchors, int pass, int db, int nblocks,
+                                                                      const int *__restrict__ hist, const int *__restrict__ key_in,
+                                                                      const int2 *__restrict__ in, int2 *__restrict__ out,
+                                                                      GEntry *__restrict__ ent, int *__restrict__ skey,
+                                                                      const Tap *__restrict__ gtap, int KD, int gtap_rows)
+{
+    extern __shared__ int ds_lds[];
+    __shared__ int wsum[DS_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ndig = 1 << db, blk = blockIdx.x;
+    int *const cnt = ds_lds, *const gbase = ds_lds + DS_WAVES * ndig;   // cnt[wave * ndig + digit], gbase[digit]
+    int k[DS_ROWS], v[DS_ROWS], loc[DS_ROWS];
+#pragma unroll
+    for (int r = 0; r < DS_ROWS; ++r) {
+        const int i = ds_elem(blk, wave, r, lane);
+        k[r] = 0, v[r] = 0;
+        if (i < nsamples) {
+            if constexpr (FIRST) {
+                k[r] = key_in[i], v[r] = i;
+            } else {
+                const int2 p = in[i];
+                k[r] = p.x, v[r] = p.y;
+            }
+        }
+    }
+    for (int d = threadIdx.x; d < DS_WAVES * ndig; d += DS_THREADS) cnt[d] = 0;
+    {   // gbase[d] = elements of all blocks with a digit < d + elements with digit d in earlier blocks
+        const int *tot = hist + ds_hist_at(ndig, 0, nblocks);
+        const int per = ndig > DS_THREADS ? ndig / DS_THREADS : 1;   // consecutive digits per thread (<= 8)
+        const int d0 = threadIdx.x * per;
+        int sum = 0;
+        for (int j = 0; j < per; ++j) sum += d0 + j < ndig ? tot[d0 + j] : 0;
+        int total;
+        int run = block_exclusive_sum(sum, wsum, &total);
+        for (int j = 0; j < per; ++j)
+            if (d0 + j < ndig) {
+                gbase[d0 + j] = run + hist[ds_hist_at(d0 + j, blk, nblocks)];
+                run += tot[d0 + j];
+            }
+    }
+    __syncthreads();
+    volatile int *cw = cnt + wave * ndig;
+#pragma unroll
+    for (int r = 0; r < DS_ROWS; ++r) {
+        const bool valid = ds_elem(blk, wave, r, lane) < nsamples;
+        const int d = ds_digit(k[r], pass, db);
+        unsigned long long m = __ballot(valid);
+        for (int b = 0; b < db; ++b) {
+            const bool bit = (d >> b) & 1;
+            const unsigned long long bal = __ballot(bit);
+            m &= bit ? bal : ~bal;
+        }
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        const int prior = valid ? cw[d] : 0;
+        loc[r] = prior + rank;
+        __builtin_amdgcn_wave_barrier();
+        if (valid && rank == 0) cw[d] = prior + __popcll(m);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < ndig; d += DS_THREADS) {   // counts -> the digit's count in the earlier waves
+        int before = 0;
+#pragma unroll
+        for (int w = 0; w < DS_WAVES; ++w) {
+            const int c = cnt[w * ndig + d];
+            cnt[w * ndig + d] = before;
+            before += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < DS_ROWS; ++r) {
+        const int i = ds_elem(blk, wave, r, lane);
+        if (i >= nsamples) continue;
+        const int d = ds_digit(k[r], pass, db);
+        const int pos = ds_position(gbase[d], cnt[wave * ndig + d], loc[r]);
+        if ((unsigned)pos >= (unsigned)nsamples) continue;
+        if constexpr (LAST) {
+            skey[pos] = k[r];
+            const int s = v[r];
+            if (k[r] != nanchors && (unsigned)s < (unsigned)nsamples) {
+                const int prow = s / KD, kd = s - prow * KD;
+                // {ly, lx, m, flags}: the second half of the sample's table entry
+                const float4 t = reinterpret_cast<const float4 *>(gtap + ((size_t)kd * gtap_rows + prow))[1];
+                GEntry e;
+                e.s = s, e.pad = __float_as_int(t.z);   // the sample's modulation scalar
+                e.ly = t.x, e.lx = t.y;
+                ent[pos] = e;
+            }
+        } else {
+            out[pos] = make_int2(k[r], v[r]);
+        }
+    }
+}
+
+// one thread per anchor (and one for the sentinel): start[a] = the first position of the sorted keys that holds a key >= a;
+// start[nanchors] = the samples on lists
+__global__ void dcn_list_starts_kernel(int nsamples, int nanchors, const int *__restrict__ skey, int *__restrict__ start)
+{
+    const int an = blockIdx.x * blockDim.x + threadIdx.x;
+    if (an > nanchors) return;
+    int lo = 0, hi = nsamples;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (skey[mid] < an) lo = mid + 1;
+        else hi = mid;
+    }
+    start[an] = lo;
+}
+
+// (tests, lsn_dcn_anchor_lists) keys with -1 for "no list", list offsets, the sample ids of the entries (-1 behind the last list)
+__global__ void dcn_list_export_kernel(int nsamples, int nanchors, const int *__restrict__ key, const int *__restrict__ start,
+                                       const GEntry *__restrict__ ent, int *__restrict__ sample_anchor, int *__restrict__ list_start,
+                                       int *__restrict__ list_sample)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nsamples) {
+        const int k = key[i];
+        sample_anchor[i] = k == nanchors ? -1 : k;
+        list_sample[i] = i < start[nanchors] ? ent[i].s : -1;
+    }
+    if (i <= nanchors) list_start[i] = start[i];
 }
 
 // One wave per 4x4 block of input pixels; lane = 4 consecutive channels (256 channels per pass).  The 5x5 anchors around

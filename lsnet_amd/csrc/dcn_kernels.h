@@ -50,7 +50,7 @@ struct DcnArgs {
     const struct Tap *gtap;   // backward: sampling table of every (pixel, tap) of the launch, k-major:
     int wg_vec;               // weight gradient: tensors admit 8-byte buffer loads (bit 0: input, bit 1: grad_output)
     int gtap_rows;            // [kd * gtap_rows + prow0 + pix], gtap_rows = pixel rows of all levels (written once by
-                              // dcn_bin_kernel; the backward kernels copy instead of recomputing)
+                              // dcn_list_keys_kernel; the backward kernels copy instead of recomputing)
     float *wg_part, *wg_part_b;   // weight gradient (dcn_wgrad_xn_kernel): per-pixel-split partial gradients [split][Co K Cg] and
                                   // [split][Co], added up by conv_wgrad_reduce_kernel in a fixed order; NULL: fp32 atomics into gw
     int mm;                   // a.wtp is in MFMA fragment order (conv_wfrag_kernel) for the kernels of dcn_mm_kernels.h
@@ -1085,7 +1085,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_data_xn_kernel(const DcnArgs a
     const Lvl &L = find_level(a, tile);
     const int tile_p = (tile - L.tile0) * BWD_BM;
 
-    if (COLBUF && a.gtap != nullptr) {   // the launch-wide table of dcn_bin_kernel (k-major): per tap, 64 entries in a row
+    if (COLBUF && a.gtap != nullptr) {   // the launch-wide table of dcn_list_keys_kernel (k-major): per tap, 64 entries in a row
         const uint4 *src = reinterpret_cast<const uint4 *>(a.gtap + (size_t)(L.prow0 + tile_p));   // 16-byte halves
         const int nvalid = min(BWD_BM, L.P - tile_p);   // tile rows past the level end stay zero = no sample
         for (int e = tid; e < BWD_BM * KD * 2; e += 256) {

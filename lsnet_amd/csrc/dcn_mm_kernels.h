@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void dcn_gout_frag_kernel(const DcnArgs a, int
     }
 }
 
-// The launch-wide sampling table (layout of dcn_bin_kernel: k-major, [kd * gtap_rows + prow0 + pix], the all-zero "no
+// The launch-wide sampling table (layout of dcn_list_keys_kernel: k-major, [kd * gtap_rows + prow0 + pix], the all-zero "no
 // sample" entry behind it) for a launch without a backward-data pass: the weight gradient of a dense convolution (Lvl.off
 // == NULL: the regular grid, every position integral) through dcn_wgrad_mm_kernel<NP, DENSE = true>.  The same launch
 // writes the per-chunk table of dcn_chunk_meta_kernel (meta != NULL).

@@ -16,7 +16,7 @@ math = sys.argv[4] if len(sys.argv) > 4 else 'bf16x6'
 FAMILY = [('dcn_fwd_', 'dcn_fwd'), ('dcn_prepare_w_kernel', 'dcn_fwd'), ('wfrag#fwd', 'dcn_fwd'),
           ('dcn_wgrad_', 'dcn_wgrad'), ('dcn_gout_frag', 'dcn_wgrad'), ('dcn_chunk_meta', 'dcn_wgrad'),
           ('conv_wgrad_reduce', 'dcn_wgrad'),
-          ('dcn_bwd_data', 'dcn_bwd_data'), ('dcn_gather', 'dcn_bwd_data'), ('dcn_bin', 'dcn_bwd_data'),
+          ('dcn_bwd_data', 'dcn_bwd_data'), ('dcn_gather', 'dcn_bwd_data'), ('dcn_list_', 'dcn_bwd_data'), ('dcn_bin', 'dcn_bwd_data'),
           ('dcn_fill', 'dcn_bwd_data'), ('dcn_sort_lists', 'dcn_bwd_data'), ('dcn_prepare_wt', 'dcn_bwd_data'),
           ('rocprim', 'dcn_bwd_data'), ('conv_mm_kernel', 'dcn_bwd_data'), ('dcn_anchor', 'dcn_bwd_data'),
           ('dcn_offgrad', 'dcn_bwd_data'), ('conv_splitk_reduce', 'dcn_bwd_data'), ('wfrag#bwd', 'dcn_bwd_data')]
