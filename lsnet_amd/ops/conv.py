@@ -4,15 +4,13 @@ mmcv/cnn/bricks/conv.py:11-43 `build_conv_layer`).
 `Conv2d` subclasses nn.Conv2d (same parameters and state-dict keys).  Every dense (groups = 1) convolution of a CUDA
 channels-last fp32 tensor -- forward, data gradient (any stride), weight and bias gradient -- runs the split-bf16
 implicit-GEMM kernels of csrc/conv_kernels.h in the library's math modes 'bf16x6' (fp32-equivalent, the default) and
-'bf16x3'.  The kernels read weights as prepared images (MFMA fragment order); `weight_image` keeps one per (weight
-tensor, pass) and rebuilds it when the tensor's version counter moves, i.e. once per optimizer step.  Grouped
+'bf16x3'.  The kernels read weights as prepared images (MFMA fragment order); `weight_image` (ops/weight_images.py) keeps
+one per (weight tensor, pass) and rebuilds it when the tensor's version counter moves, i.e. once per optimizer step.  Grouped
 convolutions with 4 .. 32 channels per group (ResNeXt 64x4d bottlenecks) run the exact-fp32 kernels of csrc/gconv.hip
 in every math mode.  Contiguous (NCHW) inputs are re-laid channels-last and LSN_MATH_FP32 runs the same fp32-equivalent
 kernels: no vendor convolution is reached from a CUDA fp32 tensor.  Other group shapes, dtypes and CPU tensors go to ATen's
 convolution, which is a different operator, not a fallback of the HIP path."""
-import ctypes
 import os
-import weakref
 
 import torch
 import torch.nn as nn
@@ -21,7 +19,8 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import ptr, stream
 from . import grad_sink
-from .streams import side_stream
+# (the cache's public names stay importable from here: the runner, the reducer, ops/resblock.py's `K` and tests take them here)
+from .weight_images import SIDE_STREAM_IMAGES, _fold_bn, invalidate_weight_images, parameters_updated, weight_image  # noqa: F401
 
 _CL = torch.channels_last
 
@@ -43,176 +42,48 @@ def _warn_aten_fallback(what, x, detail):
                   'falling back to the ATen operator', RuntimeWarning, stacklevel=3)
 
 
-def _pad_channels(t, c_to):
-    """Zero-pad dim 1 of a 4-D tensor to `c_to` channels, keeping channels-last memory."""
-    out = t.new_zeros((t.shape[0], c_to, t.shape[2], t.shape[3])).contiguous(memory_format=_CL)
-    out[:, :t.shape[1]] = t
+def _pad_channels(t, c_to, pad=0):
+    """Zero-pad dim 1 of a 4-D tensor to `c_to` channels (and dims 2, 3 by `pad` on either side), in channels-last memory."""
+    B, C, H, W = t.shape
+    out = t.new_zeros((B, c_to, H + 2 * pad, W + 2 * pad)).contiguous(memory_format=_CL)
+    out[:, :C, pad:pad + H, pad:pad + W] = t
     return out
 
 
-_images = {}    # (id(weight), kind, stride, pad, dil, math mode, id(bn) or 0) -> [weakref, version, data_ptr, image,
-#                  optimizer epoch, weakref(bn) or None, shift tensor or None, bn versions]
-_opt_epoch = [0]
+def _pad_in_channels(x, weight, pad=0):
+    """Input channels rounded up to a multiple of 4 (the 3-channel image of the stem: one zero channel and a zero column of
+    taps), the image zero-padded by `pad` pixels as well.  -> (padded x, padded weight)"""
+    C4 = (x.shape[1] + 3) // 4 * 4
+    return _pad_channels(x, C4, pad), _pad_channels(weight, C4)
 
 
-# LSNET_SIDE_STREAM_IMAGES=0: the images are rebuilt on the stream that asks for them (A/B switch)
-SIDE_STREAM_IMAGES = os.environ.get('LSNET_SIDE_STREAM_IMAGES', '1') != '0'
-_step_done = {}      # device index -> event recorded right behind the last optimizer step (on the stream that ran it)
-
-
-def _after_optimizer_step(*_):
-    """Global optimizer post-step hook: every image of a trainable weight is stale now.  (The tensors' version counters
-    are not enough: torch's FUSED optimizers update parameters without bumping them.)"""
-    _opt_epoch[0] += 1
-    if SIDE_STREAM_IMAGES and torch.cuda.is_available() and torch.cuda.is_initialized() \
-            and not torch.cuda.is_current_stream_capturing():
-        dev = torch.cuda.current_device()
-        ev = _step_done.get(dev)
-        if ev is None:
-            ev = _step_done[dev] = torch.cuda.Event()
-        ev.record()
-
-
-def parameters_updated():
-    """For optimizers that do not derive from torch.optim.Optimizer (runner/fused_sgd.py writes the parameters from its own
-    kernel): the trainable weights moved -- what the global post-step hook tells the cache for torch's optimizers."""
-    _after_optimizer_step()
-
-
-from torch.optim.optimizer import register_optimizer_step_post_hook as _reg_post_step  # noqa: E402
-
-_reg_post_step(_after_optimizer_step)
-
-
-def invalidate_weight_images():
-    """Mark EVERY cached image stale (frozen weights included).  Staleness is otherwise inferred from the tensors' version
-    counters, their storage pointers and the global optimizer post-step hook -- in-place updates through `p.data`
-    (checkpoint loading, the parameter broadcast of DataParallelModel, EMA / weight-surgery hooks, optimizers that do not
-    derive from torch.optim.Optimizer) are invisible to all three: whoever writes parameters that way calls this.
-    GraphedForwardBackward also calls it right before a capture, so that the image-rebuild launches are ALWAYS recorded
-    into the graph (captured with fresh images, every replay would run forward and data gradient on the capture-time
-    weights while the optimizer keeps moving them)."""
-    _opt_epoch[0] += 1
-    _step_done.clear()      # (the writes this call stands for came after the optimizer step: no rebuild behind its event)
-    for ent in _images.values():
-        ent[1] = -1
-
-
-def _bn_versions(bn):
-    return (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-            bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps))
-
-
-def _stale(ent, w):
-    if ent[1] != w._version or ent[2] != w.data_ptr():
-        return True
-    bn = ent[5]() if ent[5] is not None else None
-    if ent[5] is not None and (bn is None or ent[7] != _bn_versions(bn)):
-        return True
-    trainable = w.requires_grad or (bn is not None and (bn.weight.requires_grad or bn.bias.requires_grad))
-    return trainable and ent[4] != _opt_epoch[0]
-
-
-def _fill_item(it, key, ent, w):
+def _pad_narrow_co(w, gos):
+    """Data gradient under few input channels: the narrow tiles read grad_output in 4-channel pieces, so a filter count that
+    is no multiple of 4 is rounded up (zero filters are free).  -> (weight, gradients, Co) as the launch takes them."""
     Co, C, kh, kw = w.shape
-    it.kind, it.w, it.prepared = key[1], w.data_ptr(), ent[3].data_ptr()
-    it.C, it.Co, it.kh, it.kw, it.stride, it.pad, it.dil = C, Co, kh, kw, key[2], key[3], key[4]
-    bn = ent[5]() if ent[5] is not None else None
-    if bn is not None:   # a BatchNorm folded into the image (lsn_conv_wprep); the shift belongs to the forward image
-        it.bn_gamma, it.bn_var, it.bn_beta, it.bn_mean = bn.weight.data_ptr(), bn.running_var.data_ptr(), \
-            bn.bias.data_ptr(), bn.running_mean.data_ptr()
-        it.shift_out, it.bn_eps = (ent[6].data_ptr() if ent[6] is not None else None), float(bn.eps)
+    if not (Co % 4 and C <= 64):
+        return w, gos, Co
+    Co8 = (Co + 3) // 4 * 4
+    gos8 = [_pad_channels(g, Co8) for g in gos]
+    w8 = w.new_zeros((Co8, C, kh, kw)).contiguous(memory_format=_CL)
+    w8[:Co] = w
+    return w8, gos8, Co8
 
 
-def _mark_fresh(ent, w):
-    ent[1], ent[2], ent[4] = w._version, w.data_ptr(), _opt_epoch[0]
-    if ent[5] is not None and ent[5]() is not None:
-        ent[7] = _bn_versions(ent[5]())
+def _out_hw(H, W, kh, kw, stride, pad, dil):
+    return (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1, (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
 
 
-def _refresh_stale(mode):
-    """Rebuild EVERY cached image whose weight (or folded BatchNorm) has moved on -- all trainable convolutions after an
-    optimizer step -- in one launch (lsn_conv2d_prepare_weights_multi): called when the first stale image of a step is
-    asked for."""
-    items = []
-    for key, ent in _images.items():
-        w = ent[0]()
-        if w is None or key[5] != mode or (ent[5] is not None and ent[5]() is None) or not _stale(ent, w):
-            continue
-        items.append((key, ent, w))
-    if not items:
-        return
-    lib = _lib.load()
-    if torch.cuda.is_current_stream_capturing():
-        # the multi-tensor launch uploads its job table when the set of stale images changed (a synchronous copy: not
-        # allowed while a hipGraph is being captured): one launch per image instead, recorded into the graph
-        for key, ent, w in items:
-            it = _lib.ConvWprep()
-            _fill_item(it, key, ent, w)
-            _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), stream()))
-    else:
-        arr = (_lib.ConvWprep * len(items))()
-        for it, (key, ent, w) in zip(arr, items):
-            _fill_item(it, key, ent, w)
-        dev = items[0][2].device.index
-        ev = _step_done.get(dev) if SIDE_STREAM_IMAGES and len(items) > 1 else None
-        if ev is not None and not all(w.device.index == dev and ent[1] == w._version and ent[2] == w.data_ptr() and
-                                      (ent[5] is None or ent[7] == _bn_versions(ent[5]())) for _, ent, w in items):
-            # Behind the event only what the event is known to cover: every image here must be stale for ONE reason, the optimizer
-            # epoch -- same tensor version and storage as when it was built, so that no torch operation has written the weight since
-            # (any in-place write bumps the version) and the writer was the library's own optimizer kernel (runner/fused_sgd.py calls
-            # parameters_updated() right behind it).  torch's optimizers bump the versions: their steps rebuild in stream order.
-            ev = None
-        if ev is not None:
-            # The rebuild (one bandwidth-bound launch, ~0.2 ms for LSNet R-50) needs the optimizer step and nothing later: it runs on
-            # a second stream behind the event recorded there, beside whatever the asking stream has queued since -- the frozen stem
-            # and first stage of the next forward, whose images never change -- and the asking stream waits for it here.
-            main = torch.cuda.current_stream(dev)
-            side = side_stream(torch.device('cuda', dev))       # (ONE per process and device: ops/streams.py says why)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, stream()))
-            main.wait_stream(side)
-        else:
-            _lib.check(lib.lsn_conv2d_prepare_weights_multi(len(items), arr, stream()))
-    for key, ent, w in items:
-        _mark_fresh(ent, w)
-
-
-def weight_image(w, kind, stride=1, pad=0, dil=1, bn=None):
-    """The prepared image (lsn_conv2d_prepare_weights) of a channels-last (Co, C, kh, kw) weight for the forward
-    (kind 0) or backward-data (kind 1) pass.  Cached per tensor OBJECT; stale when the tensor's version counter or
-    storage moved, or -- for a trainable weight -- when any optimizer has stepped since.  The stale images of all
-    parameters are rebuilt together, once per optimizer step, when the first of them is needed; a temporary (padded
-    view, test tensor) gets a fresh one and drops it when it dies.
-    bn: an eval-mode BatchNorm2d folded into the image (every weight of forward output channel co scaled by gamma /
-    sqrt(var + eps)).  kind 0 returns (image, shift) -- the shift goes into the convolution's bias slot; kind 1 returns
-    the backward-data image of the scaled weight."""
-    lib = _lib.load()
-    mode = lib.lsn_get_math_mode()
-    key = (id(w), kind, stride, pad, dil, mode, id(bn) if bn is not None else 0)
-    ent = _images.get(key)
-    if ent is not None and ent[0]() is w and (bn is None or (ent[5] is not None and ent[5]() is bn)):
-        if _stale(ent, w):
-            _refresh_stale(mode)
-        return ent[3] if (bn is None or kind == 1) else (ent[3], ent[6])
-    Co, C, kh, kw = w.shape
-    nbytes = lib.lsn_conv2d_prepared_bytes(kind, C, Co, kh, kw, stride, pad, dil)
-    if nbytes < 0:
-        _lib.check(-2)
-    img = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-    shift = torch.empty(Co, device=w.device, dtype=torch.float32) if (bn is not None and kind == 0) else None
-    ent = [weakref.ref(w, lambda _, k=key: _images.pop(k, None)), w._version, w.data_ptr(), img, _opt_epoch[0],
-           weakref.ref(bn) if bn is not None else None, shift, _bn_versions(bn) if bn is not None else None]
-    it = _lib.ConvWprep()
-    _fill_item(it, key, ent, w)
-    _lib.check(lib.lsn_conv2d_prepare_weights_item(ctypes.byref(it), stream()))
-    _images[key] = ent
-    return img if (bn is None or kind == 1) else (img, shift)
-
-
-def _levels(n):
-    return (_lib.ConvLevel * n)()
+def _forward_prepared(x, img, bias, w_shape, stride, pad, dil, relu, residual=None):
+    """act(conv(x, the weight behind the prepared image `img`) + bias + residual) in one launch, one map."""
+    B, C, H, W = x.shape
+    Co, _, kh, kw = w_shape
+    out = torch.empty((B, Co) + _out_hw(H, W, kh, kw, stride, pad, dil), device=x.device, dtype=torch.float32, memory_format=_CL)
+    lv = (_lib.ConvLevel * 1)()
+    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = ptr(x), ptr(out), B, H, W, ptr(residual)
+    _lib.check(_lib.load().lsn_conv2d_forward_prepared(1, lv, ptr(img), ptr(bias), C, C, Co, kh, kw, stride, pad, dil,
+                                                       1 if relu else 0, stream()))
+    return out
 
 
 def _param_grad_buffers(w, bias, want_w, want_b):
@@ -287,7 +158,7 @@ def dgrad(g, w, in_shape, stride, pad, dil, bn=None, residual=None, gate=None, o
     Co, _, kh, kw = w.shape
     if out is None:
         out = torch.empty(in_shape, device=g.device, dtype=torch.float32, memory_format=_CL)
-    lv = _levels(1)
+    lv = (_lib.ConvLevel * 1)()
     lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(g), ptr(out), B, H, W
     lv[0].residual, lv[0].gate = ptr(residual), ptr(gate)
     _lib.check(_lib.load().lsn_conv2d_backward_data_prepared(1, lv, ptr(weight_image(w, 1, stride, pad, dil, bn=bn)), C, Co, kh,
@@ -353,17 +224,8 @@ def wgrad_bn_jobs(jobs, stride, pad, dil):
 
 def conv_fwd_bn(x, w, bn, stride, pad, dil, relu, residual=None):
     """act(bn_eval(conv(x, w)) + residual) in one launch (the norm folded into the prepared image)."""
-    B, C, H, W = x.shape
-    Co, _, kh, kw = w.shape
-    Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-    Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
     img, shift = weight_image(w, 0, bn=bn)
-    out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-    lv = _levels(1)
-    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = ptr(x), ptr(out), B, H, W, ptr(residual)
-    _lib.check(_lib.load().lsn_conv2d_forward_prepared(1, lv, ptr(img), ptr(shift), C, C, Co, kh, kw, stride, pad, dil,
-                                                       1 if relu else 0, stream()))
-    return out
+    return _forward_prepared(x, img, shift, w.shape, stride, pad, dil, relu, residual)
 
 
 class _ConvFn(torch.autograd.Function):
@@ -372,17 +234,8 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, pad, dil, relu):
-        lib = _lib.load()
-        B, C, H, W = x.shape
-        Co, _, kh, kw = w.shape
-        Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-        Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
         w = w.contiguous(memory_format=_CL)
-        out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-        lv = _levels(1)
-        lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(x), ptr(out), B, H, W
-        _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, ptr(weight_image(w, 0)), ptr(bias), C, C, Co, kh, kw, stride, pad,
-                                                   dil, 1 if relu else 0, stream()))
+        out = _forward_prepared(x, weight_image(w, 0), bias, w.shape, stride, pad, dil, relu)
         ctx.save_for_backward(x, w, out if relu else None)
         ctx.cfg = (stride, pad, dil, relu, bias is not None)
         ctx.bias_ref = bias    # (not saved for its value: backward only asks where its gradient goes)
@@ -401,17 +254,8 @@ class _ConvFn(torch.autograd.Function):
         Co, _, kh, kw = w.shape
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            go8, w8, Co8 = go, w, Co
-            if Co % 4 and C <= 64:    # (narrow tiles read grad_output in 4-channel pieces: zero filters are free)
-                Co8 = (Co + 3) // 4 * 4
-                go8 = _pad_channels(go, Co8)
-                w8 = w.new_zeros((Co8, C, kh, kw)).contiguous(memory_format=_CL)
-                w8[:Co] = w
-            gx = torch.empty_like(x, memory_format=_CL)
-            lv = _levels(1)
-            lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W = ptr(go8), ptr(gx), B, H, W
-            _lib.check(lib.lsn_conv2d_backward_data_prepared(1, lv, ptr(weight_image(w8, 1, stride, pad, dil)), C, Co8, kh,
-                                                             kw, stride, pad, dil, stream()))
+            w8, (go8,), _ = _pad_narrow_co(w, [go])
+            gx = dgrad(go8, w8, x.shape, stride, pad, dil)
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             # weight gradient and the bias gradient in one pass over grad_output
             want_b = has_bias and ctx.needs_input_grad[2]
@@ -430,10 +274,8 @@ class _GroupConvFn(torch.autograd.Function):
         lib = _lib.load()
         B, C, H, W = x.shape
         Co, _, kh, kw = w.shape
-        Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-        Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
         w = w.contiguous(memory_format=_CL)
-        out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
+        out = torch.empty((B, Co) + _out_hw(H, W, kh, kw, stride, pad, dil), device=x.device, dtype=torch.float32, memory_format=_CL)
         _lib.check(lib.lsn_grouped_conv2d_forward(ptr(x), ptr(w), ptr(bias), ptr(out), B, H, W, C, Co, kh, kw, stride, pad, dil,
                                                   groups, 0, stream()))
         ctx.save_for_backward(x, w)
@@ -487,8 +329,7 @@ def conv_multi_fwd(xs, w, bias, pad, dil, relu, residuals=None):
     outs = []
     for i, x in enumerate(xs):
         B, _, H, W = x.shape
-        Ho, Wo = H + 2 * pad - (dil * (kh - 1) + 1) + 1, W + 2 * pad - (dil * (kw - 1) + 1) + 1
-        out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
+        out = torch.empty((B, Co) + _out_hw(H, W, kh, kw, 1, pad, dil), device=x.device, dtype=torch.float32, memory_format=_CL)
         outs.append(out)
         L = levels[i]
         L.x, L.out, L.B, L.H, L.W = ptr(x), ptr(out), B, H, W
@@ -506,12 +347,7 @@ def conv_multi_dgrad(gos, w, xs, pad, dil, accumulate_into=None):
     launch (lsn_conv_level.residual aliasing out) and they are returned."""
     Co, C, kh, kw = w.shape
     n = len(xs)
-    w8, Co8, gos8 = w, Co, gos
-    if Co % 4 and C <= 64:    # (narrow tiles read grad_output in 4-channel pieces: zero filters are free)
-        Co8 = (Co + 3) // 4 * 4
-        gos8 = [_pad_channels(g, Co8) for g in gos]
-        w8 = w.new_zeros((Co8, C, kh, kw)).contiguous(memory_format=_CL)
-        w8[:Co] = w
+    w8, gos8, Co8 = _pad_narrow_co(w, gos)
     levels = (_lib.ConvLevel * n)()
     gxs = []
     for i, x in enumerate(xs):
@@ -612,8 +448,7 @@ def hip_conv_ok(x, weight, stride, padding, dilation, groups, padding_mode='zero
         return False
     # the output (and with it grad_output of the backward passes) must fit 32-bit byte offsets too: csrc/conv.hip conv_check
     kh, kw = weight.shape[2], weight.shape[3]
-    ho = (x.shape[2] + 2 * padding[0] - (dilation[0] * (kh - 1) + 1)) // stride[0] + 1
-    wo = (x.shape[3] + 2 * padding[1] - (dilation[1] * (kw - 1) + 1)) // stride[1] + 1
+    ho, wo = _out_hw(x.shape[2], x.shape[3], kh, kw, stride[0], padding[0], dilation[0])   # (equal along both axes: above)
     if ho <= 0 or wo <= 0 or x.shape[0] * ho * wo * weight.shape[0] * 4 >= 2 ** 31:
         return False
     return True
@@ -628,18 +463,13 @@ def _stem_forward(x, weight, bias, stride, pad, relu):
     lsn_conv2d_forward_pitched: the image is zero-padded (space: `pad`, channels: to 4) once, then a tap row of kw
     pixels x 4 channels is ONE contiguous 4 kw-float "channel" run -- kh chunks of the implicit GEMM instead of kh * kw
     chunks that are 1/8 full.  No gradient (the stem is frozen in every LSNet config)."""
-    lib = _lib.load()
-    B, C, H, W = x.shape
+    B, _, H, W = x.shape
     Co, _, kh, kw = weight.shape
-    C4 = (C + 3) // 4 * 4
-    xp = x.new_zeros((B, C4, H + 2 * pad, W + 2 * pad)).contiguous(memory_format=_CL)
-    xp[:, :C, pad:pad + H, pad:pad + W] = x
-    w4 = weight.new_zeros((Co, C4, kh, kw)).contiguous(memory_format=_CL)     # memory (Co, kh, kw, C4) = (Co, kh, 1, kw C4)
-    w4[:, :C] = weight
-    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-    out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-    _lib.check(lib.lsn_conv2d_forward_pitched(ptr(xp), ptr(w4), ptr(bias), ptr(out), None, B, H + 2 * pad, W + 2 * pad,
-                                              kw * C4, C4, Co, kh, 1, stride, 0, 1, 1 if relu else 0, stream()))
+    xp, w4 = _pad_in_channels(x, weight, pad)     # w4's memory: (Co, kh, kw, C4) = (Co, kh, 1, kw C4)
+    C4 = w4.shape[1]
+    out = torch.empty((B, Co) + _out_hw(H, W, kh, kw, stride, pad, 1), device=x.device, dtype=torch.float32, memory_format=_CL)
+    _lib.check(_lib.load().lsn_conv2d_forward_pitched(ptr(xp), ptr(w4), ptr(bias), ptr(out), None, B, H + 2 * pad, W + 2 * pad,
+                                                      kw * C4, C4, Co, kh, 1, stride, 0, 1, 1 if relu else 0, stream()))
     return out
 
 
@@ -650,32 +480,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False):
     if C < 8 and weight.shape[3] > 1 and int(dilation) == 1 and no_grad:
         return _stem_forward(x, weight, bias, int(stride), int(padding), bool(relu))
     if C % 4:    # the 3-channel image of the stem: one zero channel (and a zero column of taps)
-        C4 = (C + 3) // 4 * 4
-        x = _pad_channels(x, C4)
-        w4 = weight.new_zeros((weight.shape[0], C4, weight.shape[2], weight.shape[3])).contiguous(memory_format=_CL)
-        w4[:, :C] = weight
-        weight = w4
+        x, weight = _pad_in_channels(x, weight)
     return _ConvFn.apply(x, weight, bias, int(stride), int(padding), int(dilation), bool(relu))
-
-
-_folded = {}    # (id(conv.weight), id(bn)) -> [weakrefs, versions, folded weight, shift]
-
-
-def _fold_bn(conv, bn):
-    """(w * scale[co], shift) with scale = gamma / sqrt(var + eps), shift = beta - mean * scale: a frozen BatchNorm behind
-    a frozen convolution is the same convolution with other constants.  Rebuilt only when a tensor's version moves."""
-    key = (id(conv.weight), id(bn))
-    vers = (conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-            conv.weight.data_ptr())
-    ent = _folded.get(key)
-    if ent is not None and ent[0]() is conv.weight and ent[1]() is bn and ent[2] == vers:
-        return ent[3], ent[4]
-    with torch.no_grad():
-        scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
-        shift = (bn.bias - bn.running_mean * scale).contiguous()
-        w = (conv.weight * scale.view(-1, 1, 1, 1)).contiguous(memory_format=_CL)
-    _folded[key] = [weakref.ref(conv.weight, lambda _, k=key: _folded.pop(k, None)), weakref.ref(bn), vers, w, shift]
-    return w, shift
 
 
 def conv_bn_act_frozen(conv, bn, x, relu=True, residual=None):
@@ -703,19 +509,12 @@ def conv_bn_act_frozen(conv, bn, x, relu=True, residual=None):
         return _stem_forward(x, w, shift, stride, pad, relu)
     if C % 4:
         return None
-    Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-    Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
     if residual is not None:
-        if not (tuple(residual.shape) == (B, Co, Ho, Wo) and residual.dtype == torch.float32 and Co % 4 == 0):
+        if not (tuple(residual.shape) == (B, Co) + _out_hw(H, W, kh, kw, stride, pad, dil) and residual.dtype == torch.float32
+                and Co % 4 == 0):
             return None
         residual = _as_cl(residual)
-    lib = _lib.load()
-    out = torch.empty((B, Co, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-    lv = _levels(1)
-    lv[0].x, lv[0].out, lv[0].B, lv[0].H, lv[0].W, lv[0].residual = ptr(x), ptr(out), B, H, W, ptr(residual)
-    _lib.check(lib.lsn_conv2d_forward_prepared(1, lv, ptr(weight_image(w, 0)), ptr(shift), C, C, Co, kh, kw, stride, pad,
-                                               dil, 1 if relu else 0, stream()))
-    return out
+    return _forward_prepared(x, weight_image(w, 0), shift, w.shape, stride, pad, dil, relu, residual)
 
 
 class _ConvBnActFn(torch.autograd.Function):
@@ -772,10 +571,8 @@ def conv_bn_act(conv, bn, x, relu=True, residual=None):
     x = _as_cl(x)
     stride, pad, dil = conv.stride[0], conv.padding[0], conv.dilation[0]
     B, _, H, W = x.shape
-    Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
-    Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
     if residual is not None:
-        if not (tuple(residual.shape) == (B, Co, Ho, Wo) and residual.dtype == torch.float32):
+        if not (tuple(residual.shape) == (B, Co) + _out_hw(H, W, kh, kw, stride, pad, dil) and residual.dtype == torch.float32):
             return None
         residual = _as_cl(residual)
     return _ConvBnActFn.apply(x, conv.weight, bn.weight, bn.bias, residual, bn, stride, pad, dil, bool(relu))

@@ -189,19 +189,43 @@ class HipBackend:
         mask logits in the rest; the mask pointer is the same buffer advanced by 2*dg*K channels."""
         return om.data_ptr() + 2 * cfg['dg'] * kk * om.stride(1) * om.element_size()
 
+    def _dcn_levels(self, xs, offs, msks, w, cfg, out_hw):
+        """The lsn_dcn_level array of a call with its inputs filled in: input / offset / mask pointers and strides (the mask
+        of a fused DCNv2 pack is a view of the offsets), sizes and scales.  The caller adds its output or gradient pointers."""
+        levels = (_lib.DcnLevel * len(xs))()
+        for L, x, off, msk, (Ho, Wo), scale in zip(levels, xs, offs, msks, out_hw, cfg['scales']):
+            L.input, L.offset, L.mask = ptr(x), ptr(off), ptr(msk)
+            L.off_st = _strides(off)
+            if cfg.get('fused_om'):
+                L.mask, L.mask_st = self._mask_view_ptr(off, cfg, w.shape[2] * w.shape[3]), _strides(off)
+            elif msk is not None:
+                L.mask_st = _strides(msk)
+            L.B, L.H, L.W, L.Ho, L.Wo = x.shape[0], x.shape[2], x.shape[3], Ho, Wo
+            L.scale_h, L.scale_w = scale
+        return levels
+
     @staticmethod
-    def _cached_image(w, weight, cfg, kind, nhwc):
-        """The fragment image of a deformable layer's weight from the per-optimizer-step cache of the dense convolutions
-        (ops/conv.py weight_image; kind 0: forward, 2: the backward GEMM) -- only for a channels-last PARAMETER handed over as it is
-        (a temporary's image would be built and dropped per call: the in-call build is cheaper), groups = 1.  None: build per call.
-        The library has the last word (lsn_dcn_prepared_ok)."""
-        if not (CACHE_DCN_IMAGES and nhwc and w is weight and cfg['groups'] == 1 and isinstance(weight, torch.nn.Parameter)):
-            return None
-        from .conv import weight_image
-        try:
-            return weight_image(w, kind, 1, cfg['pad'], cfg['dil'])
-        except NotImplementedError:
-            return None
+    def _weight_workspace(shape, levels, w, weight, cfg, nhwc, backward):
+        """Sets shape.workspace (and weights_prepared) of a split-math call and returns the tensor behind it: the weight's
+        fragment image from the per-optimizer-step cache (ops/weight_images.py; kind 0: forward, 2: the backward GEMM) or the
+        call's own scratch for the split weight planes.  The cache serves a channels-last PARAMETER handed over as it is (a
+        temporary's image would be built and dropped per call), groups = 1, and only after the library said that this call reads
+        a prepared image (lsn_dcn_prepared_ok; its routing reads `workspace` as a flag, and in the backward pass needs the gather
+        workspace in `shape`): the cache holds no image that no call reads."""
+        if CACHE_DCN_IMAGES and nhwc and w is weight and cfg['groups'] == 1 and isinstance(weight, torch.nn.Parameter):
+            shape.workspace, shape.weights_prepared = w.data_ptr(), 1
+            if _lib.load().lsn_dcn_prepared_ok(ctypes.byref(shape), len(levels), levels, 1 if backward else 0):
+                from .weight_images import weight_image
+                try:
+                    img = weight_image(w, 2 if backward else 0, 1, cfg['pad'], cfg['dil'])
+                    shape.workspace = img.data_ptr()
+                    return img
+                except NotImplementedError:
+                    pass
+            shape.weights_prepared = 0      # (a cached image must not be written: own scratch)
+        ws = torch.empty(2 * w.numel(), device=w.device, dtype=torch.float32)
+        shape.workspace = ws.data_ptr()
+        return ws
 
     def dcn_forward(self, inputs, offsets, masks, weight, bias, cfg, out_hw):
         """inputs/offsets/masks: per-level lists (mask entries may be None); cfg: stride, pad, dil,
@@ -210,7 +234,7 @@ class HipBackend:
         nhwc, xs, offs, msks, w = self._prep(inputs, offsets, masks, weight)
         n = len(xs)
         shape = self._shape(w, cfg)
-        levels = (_lib.DcnLevel * n)()
+        levels = self._dcn_levels(xs, offs, msks, w, cfg, out_hw)
         outs = []
         # cfg['concat'] = g: the outputs of g consecutive levels are wanted side by side in ONE (B, g Co, Ho, Wo) tensor (LSHead:
         # the three maps a level gathers, lsnet_head.py:640-647).  The kernels write them there (lsn_dcn_shape.out_pitch)
@@ -224,33 +248,16 @@ class HipBackend:
                 wide = [torch.empty((xs[j].shape[0], g * Co) + tuple(out_hw[j]), device=xs[j].device, dtype=torch.float32,
                                     memory_format=_CL) for j in range(0, n, g)]
         for i in range(n):
-            B, C, H, W = xs[i].shape
-            Ho, Wo = out_hw[i]
             if wide is not None:
                 out = wide[i // g].narrow(1, (i % g) * Co, Co)
             else:
-                out = torch.empty((B, Co, Ho, Wo), device=xs[i].device, dtype=torch.float32,
+                out = torch.empty((xs[i].shape[0], Co) + tuple(out_hw[i]), device=xs[i].device, dtype=torch.float32,
                                   memory_format=_CL if nhwc else torch.contiguous_format)
             outs.append(out)
-            L = levels[i]
-            L.input, L.offset, L.mask, L.output = ptr(xs[i]), ptr(offs[i]), ptr(msks[i]), ptr(out)
-            L.off_st = _strides(offs[i])
-            if cfg.get('fused_om'):
-                L.mask, L.mask_st = self._mask_view_ptr(offs[i], cfg, w.shape[2] * w.shape[3]), _strides(offs[i])
-            elif msks[i] is not None:
-                L.mask_st = _strides(msks[i])
-            L.B, L.H, L.W, L.Ho, L.Wo = B, H, W, Ho, Wo
-            L.scale_h, L.scale_w = cfg['scales'][i]
+            levels[i].output = ptr(out)
         b = None if bias is None else _f32(bias.contiguous(), 'bias')
-        if _lib.split_math():
-            img = self._cached_image(w, weight, cfg, 0, nhwc)
-            if img is not None:
-                shape.workspace, shape.weights_prepared = img.data_ptr(), 1
-                if not lib.lsn_dcn_prepared_ok(ctypes.byref(shape), n, levels, 0):
-                    img, shape.weights_prepared = None, 0
-            if img is None:
-                ws = torch.empty(2 * w.numel(), device=w.device, dtype=torch.float32)   # pre-split weight planes
-                shape.workspace = ws.data_ptr()
+        if _lib.split_math():    # the weight's image, or scratch for its pre-split planes (held until the launch)
+            ws = self._weight_workspace(shape, levels, w, weight, cfg, nhwc, False)  # noqa: F841
         if wide is not None:
             shape.out_pitch = g * Co
             if not lib.lsn_dcn_pitched_ok(ctypes.byref(shape), n, levels, 0):   # (exact-fp32 mode, odd channel counts)
@@ -312,43 +319,19 @@ class HipBackend:
         lib = _lib.load()
         n = len(xs)
         shape = self._shape(w, cfg)
-        levels = (_lib.DcnLevel * n)()
-        for i in range(n):
-            B, C, H, W = xs[i].shape
-            go, gx, goff, gmsk = gos[i], gx_bufs[i], goffs[i], gmsks[i]
-            Ho, Wo = go.shape[2], go.shape[3]
-            L = levels[i]
-            L.input, L.offset, L.mask = ptr(xs[i]), ptr(offs[i]), ptr(msks[i])
+        levels = self._dcn_levels(xs, offs, msks, w, cfg, [g.shape[2:] for g in gos])
+        for L, go, gx, goff, gmsk in zip(levels, gos, gx_bufs, goffs, gmsks):
             L.grad_output, L.grad_input, L.grad_offset, L.grad_mask = ptr(go), ptr(gx), ptr(goff), ptr(gmsk)
-            L.off_st = _strides(offs[i])
-            if cfg.get('fused_om'):
-                kk = w.shape[2] * w.shape[3]
-                L.mask, L.mask_st = self._mask_view_ptr(offs[i], cfg, kk), _strides(offs[i])
-                if goff is not None:   # one gradient tensor for offsets + mask logits
-                    L.grad_mask = self._mask_view_ptr(goff, cfg, kk)
-            elif msks[i] is not None:
-                L.mask_st = _strides(msks[i])
-            L.B, L.H, L.W, L.Ho, L.Wo = B, H, W, Ho, Wo
-            L.scale_h, L.scale_w = cfg['scales'][i]
-        ws = gws = None
-        img = self._cached_image(w, weight, cfg, 2, nhwc) if _lib.split_math() else None
-        if img is not None:
-            shape.workspace = img.data_ptr()       # (weights_prepared is decided below, when the gather workspace is known)
-        elif cfg['groups'] == 1 and _lib.split_math():
-            ws = torch.empty(2 * w.numel(), device=w.device, dtype=torch.float32)   # split + transposed weight planes
-            shape.workspace = ws.data_ptr()
+            if cfg.get('fused_om') and goff is not None:   # one gradient tensor for offsets + mask logits
+                L.grad_mask = self._mask_view_ptr(goff, cfg, w.shape[2] * w.shape[3])
         # column-gradient buffer + anchor lists of the atomic-free grad_input path, in every math mode (round 6: the exact mode's
         # column gradients are fmaf chains in front of the same gather; 0 bytes: a shape only the scatter kernels serve)
         nbytes = int(lib.lsn_dcn_backward_workspace_bytes(ctypes.byref(shape), n, levels))
         if nbytes > 0:
             gws = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
             shape.gather_workspace, shape.gather_workspace_bytes = gws.data_ptr(), nbytes
-        if img is not None:
-            shape.weights_prepared = 1
-            if not lib.lsn_dcn_prepared_ok(ctypes.byref(shape), n, levels, 1):   # (the cached image must not be written: own scratch)
-                shape.weights_prepared = 0
-                ws = torch.empty(2 * w.numel(), device=w.device, dtype=torch.float32)
-                shape.workspace = ws.data_ptr()
+        if cfg['groups'] == 1 and _lib.split_math():    # the weight's image, or scratch for its split + transposed planes
+            ws = self._weight_workspace(shape, levels, w, weight, cfg, nhwc, True)  # noqa: F841
         shape.accumulate_param_grads = 1 if accumulate else 0
         pitch = _pixel_pitch(gos[0]) if nhwc else None
         if pitch is not None and pitch != w.shape[0]:

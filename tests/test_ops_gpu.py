@@ -1388,6 +1388,79 @@ def test_dcn_weight_images_cached_per_optimizer_step():
             w.add_(0.01)          # the version counter moves: the cached images are stale and rebuilt on the next call
 
 
+def _dcn_prepared_kinds(w, x, off, msk, go, backward):
+    """The image kinds lsn_dcn_prepared_ok ITSELF admits for one 3 x 3, pad 1, dg = 1 channels-last level: 0 for the forward,
+    2 for the backward (backward: None = no backward pass, 'weight' = only grad_weight is asked for, 'all' = every gradient)."""
+    from lsnet_amd.ops.hip_backend import HipBackend, _ptr, _strides
+    lib = _lib.load()
+    keep = [torch.empty_like(go), torch.empty_like(x), torch.empty_like(off), torch.empty_like(msk)]
+    kinds = set()
+    for bwd in ((0,) if backward is None else (0, 1)):
+        shape = HipBackend._shape(w, dict(stride=1, pad=1, dil=1, groups=1, dg=1))
+        levels = (_lib.DcnLevel * 1)()
+        L = levels[0]
+        L.input, L.offset, L.mask, L.off_st, L.mask_st = _ptr(x), _ptr(off), _ptr(msk), _strides(off), _strides(msk)
+        L.B, L.H, L.W, L.Ho, L.Wo = x.shape[0], x.shape[2], x.shape[3], x.shape[2], x.shape[3]
+        L.scale_h = L.scale_w = 1.0
+        shape.workspace, shape.weights_prepared = w.data_ptr(), 1      # (the routing reads `workspace` as a flag)
+        if not bwd:
+            L.output = _ptr(keep[0])
+        else:
+            L.grad_output = _ptr(go)
+            if backward == 'all':
+                L.grad_input, L.grad_offset, L.grad_mask = _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3])
+            nbytes = int(lib.lsn_dcn_backward_workspace_bytes(ctypes.byref(shape), 1, levels))
+            if nbytes > 0:
+                keep.append(torch.empty(nbytes, device=x.device, dtype=torch.uint8))
+                shape.gather_workspace, shape.gather_workspace_bytes = keep[-1].data_ptr(), nbytes
+        if lib.lsn_dcn_prepared_ok(ctypes.byref(shape), 1, levels, bwd):
+            kinds.add(2 if bwd else 0)
+    return kinds
+
+
+@pytest.mark.parametrize('C,backward,held', [(64, None, set()), (256, 'weight', {0}), (256, 'all', {0, 2})])
+def test_dcn_cache_holds_only_the_images_the_library_reads(C, backward, held):
+    """The deformable binding asks lsn_dcn_prepared_ok BEFORE it registers an image: the cache holds the
+    kinds the library says it reads for the call -- none for Co = 64 (Co % 128 != 0), only the forward's when the backward
+    forms no data gradient -- and nothing else; the reference is the library's own answer for the shape.  Results: the bits
+    of the uncached call."""
+    from lsnet_amd import ops
+    from lsnet_amd.ops import hip_backend
+    from lsnet_amd.ops.weight_images import cached_kinds
+    dev = _dev()
+    g = torch.Generator().manual_seed(52)
+    old_mode = _lib.get_math_mode()
+    _lib.set_math_mode('bf16x6')
+    try:
+        w = torch.nn.Parameter(_to(torch.randn(C, C, 3, 3, generator=g) / (3 * C ** 0.5), dev, True))
+        x, off, msk, go = (_to(t, dev, True) for t in (torch.randn(1, C, 6, 7, generator=g), torch.randn(1, 18, 6, 7, generator=g) * 1.5,
+                                                        torch.rand(1, 9, 6, 7, generator=g), torch.randn(1, C, 6, 7, generator=g)))
+        if backward == 'all':
+            x.requires_grad_(), off.requires_grad_(), msk.requires_grad_()
+        wanted = [w] if backward == 'weight' else [w, x, off, msk]
+
+        def run(cached):
+            old = hip_backend.CACHE_DCN_IMAGES
+            hip_backend.CACHE_DCN_IMAGES = cached
+            try:
+                out, = ops.dcn_multi([x], [off], [msk], w, None, 1, 1, 1)
+                grads = torch.autograd.grad([out], wanted, [go]) if backward else []
+                return [out.detach().clone()] + [t.clone() for t in grads]
+            finally:
+                hip_backend.CACHE_DCN_IMAGES = old
+
+        ref = run(False)
+        assert cached_kinds(w) == set()
+        got = run(True)
+        expect = _dcn_prepared_kinds(w, x, off, msk, go, backward)
+        print(f'C = Co = {C}, backward {backward}: the library reads kinds {sorted(expect)}, the cache holds {sorted(cached_kinds(w))}')
+        assert expect == held and cached_kinds(w) == expect
+        for k, (a, c) in enumerate(zip(ref, got)):
+            assert torch.equal(a, c), k
+    finally:
+        _lib.set_math_mode(old_mode)
+
+
 @pytest.mark.parametrize('mode', ['bf16x6', 'fp32'])
 def test_pyramid_outputs_side_by_side(mode):
     """`concat=3` of the pyramid op (lsn_dcn_shape.out_pitch: the three maps of a destination level written into one
