@@ -99,7 +99,8 @@ class CrossIOULoss(nn.Module):
             assert weight.shape == pred.shape
             weight = weight.mean(-1)
         from ...ops import cross_iou as fused
-        if fused.enabled() and fused.usable(pred, target, self.loss_type) and kwargs.get('pos_inds') is not None:
+        if fused.enabled() and fused.usable(pred, target, self.loss_type, kwargs.get('pos_inds'), kwargs.get('anchor_pts'),
+                                            kwargs.get('bbox_gt'), weight):
             from .utils import weight_reduce_loss
             rows = fused.cross_iou_bbox_rows(pred, target, kwargs['pos_inds'], kwargs['anchor_pts'], kwargs['bbox_gt'],
                                              weight, self.alpha, self.eps)      # already weighted

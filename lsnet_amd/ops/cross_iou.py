@@ -2,7 +2,8 @@
 elementwise launches of the torch formulation (models/losses/cross_iou_loss.py) -- the bbox task
 (lsn_cross_iou_bbox_forward / _backward and the whole-stage variant), the polygon (instance segmentation) and the
 keypoint (pose) tasks (lsn_cross_iou_rows_forward / _backward).  On by default for device tensors (verified on the MI355X against the torch
-formulation and the reference fixture: tests/test_zz_fused_ciou_gpu.py); `LSNET_FUSED_CIOU=0` keeps the torch formulation."""
+formulation and the reference fixture: tests/test_zz_fused_ciou_gpu.py; against float64 at negative predictions, ties and odd
+storage: tests/test_loss_edges_gpu.py); `LSNET_FUSED_CIOU=0` keeps the torch formulation."""
 import os
 
 import torch
@@ -15,11 +16,24 @@ def enabled():
     return os.environ.get('LSNET_FUSED_CIOU', '1') != '0'
 
 
+def _rows16(t):
+    """`t` as contiguous rows at a 16-byte aligned address, as the bbox / stage kernels' float4 accesses need them.
+    `.contiguous()` leaves a contiguous view at an odd element offset (buf[1:].view(n, 20)) where it is: that one is copied."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def shapes_match(pred, want):
+    """`want`: (tensor or None, shape) pairs.  True when every tensor given has its shape and lies on pred's device.  The
+    kernels index their side tensors unchecked, so this is what keeps a short buffer away from them."""
+    return all(t is None or (tuple(t.shape) == tuple(shape) and t.device == pred.device) for t, shape in want)
+
+
 class _CrossIouBbox(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, active, anchor, bbox_gt, weight, alpha, eps):
-        pred, target = pred.contiguous(), target.contiguous()
+        pred, target = _rows16(pred), _rows16(target)
         active = active.to(torch.uint8).contiguous()
         anchor, bbox_gt = anchor.contiguous(), bbox_gt.contiguous()
         weight = None if weight is None else weight.contiguous()
@@ -43,9 +57,17 @@ class _CrossIouBbox(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None
 
 
-def usable(pred, target, loss_type):
-    return (loss_type == 'bbox' and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2
-            and pred.shape[1] == 20 and not target.requires_grad)
+def usable(pred, target, loss_type, active=None, anchor=None, bbox_gt=None, weight=None):
+    """The bbox kernels: rows of 20 fp32 components on the device, with every side tensor they index (active[20 i],
+    anchor[2 i], bbox_gt[4 i], weight[i]) present and of matching shape.  A mismatch sends the caller to the torch formulation,
+    which raises the ordinary shape error."""
+    if not (loss_type == 'bbox' and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2
+            and pred.shape[1] == 20 and not target.requires_grad):
+        return False
+    if active is None or anchor is None or bbox_gt is None:
+        return False
+    n = pred.shape[0]
+    return shapes_match(pred, ((target, (n, 20)), (active, (n, 20)), (anchor, (n, 2)), (bbox_gt, (n, 4)), (weight, (n,))))
 
 
 _KIND = {'polygon': 1, 'keypoint': 2}
@@ -61,11 +83,8 @@ def rows_usable(pred, target, loss_type, stride=9, active=None, anchor=None, bbo
             and (loss_type == 'keypoint' or 1 <= stride <= min(16, pred.shape[1] // 4))):
         return False
     n, m = pred.shape
-    want = ((target, (n, m)), (active, (n, m)), (anchor, (n, 2)), (bbox_gt, (n, 4)), (vs, (n, m // 4 - 1)), (weight, (n,)))
-    for t, shape in want:
-        if t is not None and (tuple(t.shape) != shape or t.device != pred.device):
-            return False
-    return True
+    return shapes_match(pred, ((target, (n, m)), (active, (n, m)), (anchor, (n, 2)), (bbox_gt, (n, 4)), (vs, (n, m // 4 - 1)),
+                               (weight, (n,))))
 
 
 class _CrossIouRows(torch.autograd.Function):
@@ -114,7 +133,7 @@ class _CrossIouBboxStage(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, gt_pts, anchor3, bbox_gt, weight, base, alpha, eps):
-        raw, gt_pts, anchor3 = raw.contiguous(), gt_pts.contiguous(), anchor3.contiguous()
+        raw, gt_pts, anchor3 = _rows16(raw), gt_pts.contiguous(), anchor3.contiguous()
         bbox_gt, weight = bbox_gt.contiguous(), weight.contiguous()
         loss = torch.empty(raw.shape[0], dtype=torch.float32, device=raw.device)
         _lib.check(_lib.load().lsn_cross_iou_bbox_stage_forward(ptr(raw), ptr(gt_pts), ptr(anchor3), ptr(bbox_gt), ptr(weight),
@@ -138,4 +157,9 @@ class _CrossIouBboxStage(torch.autograd.Function):
 def cross_iou_bbox_stage_rows(pred_raw, gt_pts, anchor3, bbox_gt, weight, base_scale, alpha=0.2, eps=1e-6):
     """The bbox regression stage of LSHead for n points in one launch (see lsn_cross_iou_bbox_stage_forward): weighted
     loss rows; gradient flows to `pred_raw`."""
+    n = pred_raw.shape[0]
+    if pred_raw.dim() != 2 or pred_raw.shape[1] != 20 or not shapes_match(
+            pred_raw, ((gt_pts, (n, 10)), (anchor3, (n, 3)), (bbox_gt, (n, 4)), (weight, (n,)))):
+        raise ValueError(f'cross_iou_bbox_stage_rows: {tuple(pred_raw.shape)} predictions beside points {tuple(gt_pts.shape)}, '
+                         f'anchors {tuple(anchor3.shape)}, boxes {tuple(bbox_gt.shape)} and weights {tuple(weight.shape)}')
     return _CrossIouBboxStage.apply(pred_raw, gt_pts, anchor3, bbox_gt, weight, float(base_scale), float(alpha), float(eps))

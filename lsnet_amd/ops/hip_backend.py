@@ -345,6 +345,22 @@ class HipBackend:
                                         1 if nhwc else 0, stream()))
 
     # ------------------------------------------------------------------ sigmoid focal loss
+    @staticmethod
+    def _focal_rows(logits, targets, weight=None, d_losses=None):
+        """(N, C) of the logits, after checking what the kernels index unchecked: targets[n], weight[n], d_losses[n, c]"""
+        if logits.dim() != 2:
+            raise ValueError(f'focal loss: logits must be (N, C), got {tuple(logits.shape)}')
+        N, C = logits.shape
+        if targets.dtype != torch.int64:
+            raise TypeError('targets must be int64')
+        if targets.numel() != N or targets.device != logits.device:
+            raise ValueError(f'focal loss: {targets.numel()} targets on {targets.device} for {N} rows of logits on {logits.device}')
+        if weight is not None and (weight.numel() != N or weight.device != logits.device):
+            raise ValueError(f'focal loss: {weight.numel()} weights on {weight.device} for {N} rows of logits on {logits.device}')
+        if d_losses is not None and (d_losses.shape != logits.shape or d_losses.device != logits.device):
+            raise ValueError(f'focal loss: upstream gradient {tuple(d_losses.shape)} for logits {tuple(logits.shape)}')
+        return N, C
+
     def focal_forward(self, logits, targets, gamma, alpha):
         lib = _lib.load()
         logits = _f32(logits, 'logits').contiguous()
@@ -352,7 +368,7 @@ class HipBackend:
         if targets.dtype != torch.int64:
             raise TypeError('targets must be int64')
         out = torch.empty_like(logits)
-        N, C = logits.shape
+        N, C = self._focal_rows(logits, targets)
         _lib.check(lib.lsn_sigmoid_focal_loss_forward(ptr(logits), ptr(targets), ptr(out), N, C, gamma, alpha,
                                                       stream()))
         return out
@@ -362,7 +378,7 @@ class HipBackend:
         logits = logits.contiguous()
         d_losses = d_losses.contiguous()
         out = torch.empty_like(logits)
-        N, C = logits.shape
+        N, C = self._focal_rows(logits, targets, d_losses=d_losses)
         _lib.check(lib.lsn_sigmoid_focal_loss_backward(ptr(logits), ptr(targets.contiguous()), ptr(d_losses),
                                                        ptr(out), N, C, gamma, alpha, stream()))
         return out
@@ -371,7 +387,7 @@ class HipBackend:
         lib = _lib.load()
         logits = _f32(logits, 'logits').contiguous()
         out = torch.empty((), device=logits.device, dtype=torch.float32)
-        N, C = logits.shape
+        N, C = self._focal_rows(logits, targets, weight)
         w = None if weight is None else _f32(weight, 'weight').contiguous()
         _lib.check(lib.lsn_sigmoid_focal_loss_sum(ptr(logits), ptr(targets.contiguous()), ptr(w), ptr(out), N,
                                                   C, gamma, alpha, stream()))
@@ -381,7 +397,7 @@ class HipBackend:
         lib = _lib.load()
         logits = logits.contiguous()
         out = torch.empty_like(logits)
-        N, C = logits.shape
+        N, C = self._focal_rows(logits, targets, weight)
         w = None if weight is None else weight.contiguous()
         scale = scale.to(torch.float32).contiguous()
         _lib.check(lib.lsn_sigmoid_focal_loss_backward_weighted(
