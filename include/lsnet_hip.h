@@ -611,7 +611,7 @@ enum {
     LSN_DBG_WG_COMPUTED_TAPS = 1 << 24, /* weight gradient: rebuild the sampling table, not the backward's table  */
     LSN_DBG_WG_SCALAR_LOADS = 1 << 25,  /* weight gradient: scalar loads instead of 8-byte ones                   */
     LSN_DBG_GENERAL_GEMMS = 1 << 28     /* no kernel of dcn_mm_kernels.h: dcn_kernels.h only, and the dense weight
-                                         * gradient on the patch kernel of conv_wgrad_kernels.h                   */
+                                         * gradient never on CW_DENSE_MM (csrc/conv_wgrad_route.h)                */
 };
 /* When device_buf_512 is a device buffer of 512 int64 (NULL disables), thread 0 of workgroup `word & LSN_DBG_BLOCK_MASK`
  * of the next DCN forward / backward-data launches appends (phase_id << 56 | shader_clock) stamps at its phase

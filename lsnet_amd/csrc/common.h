@@ -30,6 +30,8 @@ int fail(int code, const char *fmt, ...);
     } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// output size of a convolution along one axis
+static inline int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 // v_mfma_f32_32x32x2_f32: D(32x32) += A(32x2) * B(2x32).
 //   lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31];

@@ -8,7 +8,8 @@
 //   forward      : out[p][co] = sum_{tap, ci} x[p @ tap][ci] * w[co][tap][ci] (+ bias, ReLU); up to 8 maps per launch
 //   backward-data: the same kernel on grad_output with the weights transposed and flipped; a stride-s convolution is
 //                  s x s stride-1 convolutions over tap subsets (TapSub), each writing its residue class of input pixels
-//   backward-weight: dcn_wgrad_xn_kernel<PLAIN = true> (dcn_kernels.h), reduction over pixels with px-contiguous LDS images
+//   backward-weight: one of three kernels by conv_wgrad_route.h -- the patch kernel of conv_wgrad_kernels.h here, the
+//                  fragment-order and the general kernel of the deformable family through dcn.hip's two launchers
 //
 // Weights reach the kernel in MFMA fragment order (conv_wfrag_kernel), written by lsn_conv2d_prepare_weights -- once per
 // optimizer step when the caller keeps the image (the Python mirror caches it per parameter version), or inside the
@@ -327,16 +328,14 @@ struct LaunchLog {
     LaunchLog &operator=(const LaunchLog &) = delete;
 };
 
-static int conv_out_size(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
-
 static int conv_check(int B, int H, int W, int C, int Co, int kh, int kw, int stride, int pad, int dil, int *Ho,
                       int *Wo)
 {
     LSN_CHECK(B > 0 && H > 0 && W > 0 && C > 0 && Co > 0 && kh > 0 && kw > 0, "conv2d: empty tensor");
     LSN_CHECK(stride > 0 && dil > 0 && pad >= 0, "conv2d: bad stride / dilation / padding");
     if (kh * kw > 64) return fail(LSN_ERR_UNSUPPORTED, "conv2d kernel takes at most 64 taps, got %d x %d", kh, kw);
-    *Ho = conv_out_size(H, kh, stride, pad, dil);
-    *Wo = conv_out_size(W, kw, stride, pad, dil);
+    *Ho = conv_out(H, kh, stride, pad, dil);
+    *Wo = conv_out(W, kw, stride, pad, dil);
     LSN_CHECK(*Ho > 0 && *Wo > 0, "conv2d: output size is too small");
     if ((int64_t)B * H * W * C * 4 >= ((int64_t)1 << 31) || (int64_t)Co * kh * kw * C * 4 >= ((int64_t)1 << 31) ||
         (int64_t)B * *Ho * *Wo * Co * 4 >= ((int64_t)1 << 31))
@@ -559,20 +558,21 @@ static int prepare_weights(int kind, const float *w, void *prepared, int C, int 
 }
 
 // ---- weight / bias gradient (conv_wgrad_kernels.h) ----
-// (state of a folded-norm weight-gradient call, see conv_wgrad_reduce below)
-static thread_local const WgFoldJobs *g_wg_fold = nullptr;
-bool conv_wgrad_fold_pending() { return g_wg_fold != nullptr; }
-static int wg_jobs() { return g_wg_fold ? g_wg_fold->njobs : 1; }
+static_assert(CW_MAXLV <= CV_MAXLV, "WgArgs holds every level of a validated call");
+static int fold_jobs(const WgFoldJobs *fold) { return fold ? fold->njobs : 1; }
+
+// UN_OK: the configuration also serves Co % 4 != 0 (conv_wgrad_route.h sends no other one such a call)
 template <int TI, int TJ, int TG, int WI, int WJ, int PMAX, bool UN_OK>
-static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hipStream_t st)
+static int launch_wgrad_cfg(WgArgs &a, const ConvWgradCall &c, hipStream_t st)
 {
+    float *const gw = c.gw, *const gb = c.gb;
     const bool un = a.Co % 4 != 0;
-    if (un && !UN_OK) return 1;
+    LSN_CHECK(UN_OK || !un, "conv2d backward-weight: Co = %d on an aligned configuration of the patch kernel", a.Co);
     constexpr int BN = WI * TI * 32, BM = WJ * TJ * 32;
     const int npl = conv_npl(), K = a.kh * a.kw;
     const int blocks = cdiv(a.Co, BM) * cdiv(a.C, BN);
     const size_t nW = (size_t)a.Co * K * a.C;
-    const int nj = wg_jobs();   // > 1: the levels are jobs with their own outputs; every split stays inside one level
+    const int nj = fold_jobs(c.fold);   // > 1: the levels are jobs with their own outputs; every split stays inside one level
     int S = 512 / (blocks * nj);   // one round of workgroups (rounds 3 / 4 rounded to nearest: 516 .. 540 on 512 slots)
     const size_t cap = ((size_t)192 << 20) / 4 / (nW + a.Co) / nj;   // partial tiles: at most 192 MB
     if ((size_t)S > cap) S = (int)cap;
@@ -585,8 +585,9 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     a.part_b = part + (((size_t)S * nW + 3) & ~(size_t)3);
     a.want_bias = gb != nullptr;
     constexpr int XP = 1024 / BN, GP = 1024 / BM;   // pixels per staging pass (conv_wgrad_kernel)
-    const size_t lds = (size_t)2 * npl * ((size_t)cdiv(PMAX, XP) * XP * BN * 2 + (size_t)cdiv(16, GP) * GP * BM * 2);
-    if (lds > 160 * 1024) return 1;
+    constexpr size_t lds_plane = (size_t)2 * ((PMAX + XP - 1) / XP * XP * BN * 2 + (16 + GP - 1) / GP * GP * BM * 2);
+    static_assert(lds_plane <= 32 * 1024, "three planes per operand stay below the 160 KB of a workgroup");
+    const size_t lds = lds_plane * npl;
     dim3 grid(blocks, S);
     LSN_CHECK((long long)a.nseg * (S + 1) < (1ll << 32), "conv2d backward-weight: %d segments x %d splits exceed the kernel's 32-bit split arithmetic", a.nseg, S);
     auto launch = [&](auto kern) -> int {
@@ -600,7 +601,7 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
     constexpr bool FINE = !(TG == 9 && WI == 4);
     rc = split_dispatch(conv_np(), [&](auto np) {
         constexpr int NP = decltype(np)::value;
-        if constexpr (NP == 1 && TG == 9 && WI == 4) {   // (not instantiated: see conv_wgrad_mm)
+        if constexpr (NP == 1 && TG == 9 && WI == 4) {   // (not instantiated: see cw_patch_ok)
             return fail(LSN_ERR_INVALID, "conv2d backward-weight: no one-product form of the narrow 3x3 kernel");
         } else {
             if constexpr (UN_OK) {
@@ -610,7 +611,7 @@ static int launch_wgrad_cfg(WgArgs &a, float *gw, float *gb, int accumulate, hip
         }
     });
     if (rc) return rc;
-    return conv_wgrad_reduce(a.part, gw, nW, a.part_b, gb, a.Co, S, S, accumulate, st);
+    return conv_wgrad_reduce(a.part, gw, nW, a.part_b, gb, a.Co, S, S, c.accumulate, c.fold, st);
 }
 
 // Lanes that share a float4 of the reduce: each sums PER_LANE partial tiles on its own before the xor-shuffles (>= PER_LANE / 2
@@ -624,15 +625,13 @@ static int reduce_ls(int splits)
     return LS;
 }
 
-// dcn.hip: gw (+)= sum of `splits` partial gradients of n floats (n % 4 == 0), gb (+)= sum of splits_b partial rows of nb
-// With a BatchNorm fold pending (lsn_conv2d_backward_weight_bn set g_wg_fold for the duration of its weight-gradient
-// call) the reduce also applies the norm's scale and forms grad_gamma / grad_beta (conv_wgrad_reduce_bn_kernel); gb is then
-// the entry point's dummy bias gradient (it only makes the main kernels write the per-channel sums of g).
+// lib_state.h.  With a fold, gb is the entry point's dummy bias gradient (it only makes the main kernels write the per-channel
+// sums of g) and conv_wgrad_reduce_bn_kernel is the only writer of grad_w / grad_gamma / grad_beta.
 int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_b, float *gb, int nb, int splits, int splits_b,
-                      int accumulate, hipStream_t st)
+                      int accumulate, const WgFoldJobs *fold, hipStream_t st)
 {
-    const int nj = wg_jobs();   // (splits / splits_b count ALL jobs' partial tiles)
-    if (g_wg_fold)
+    const int nj = fold_jobs(fold);   // (splits / splits_b count ALL jobs' partial tiles)
+    if (fold)
         LSN_CHECK(part_b && nb > 0 && n % ((size_t)nb * 4) == 0 && splits % nj == 0 && splits_b % nj == 0,
                   "conv2d backward-weight (folded norm): bad partial layout");
     if (Arena *ar = accumulate ? deferring(st) : nullptr) {
@@ -641,18 +640,18 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
         bool clash = false;
         for (const RJob &q : *ar->jobs)
             for (int j = 0; j < nj; ++j) {
-                const float *tw = g_wg_fold ? (nj > 1 ? g_wg_fold->gw[j] : gw) : gw;
-                clash = clash || q.gw == tw || (gb && q.gb == gb) || (g_wg_fold && q.fold && q.f.dgamma == g_wg_fold->f[j].dgamma);
+                const float *tw = fold ? (nj > 1 ? fold->gw[j] : gw) : gw;
+                clash = clash || q.gw == tw || (gb && q.gb == gb) || (fold && q.fold && q.f.dgamma == fold->f[j].dgamma);
             }
         if (clash)
             if (int rc = wgrad_flush(ar)) return rc;   // (the arena is NOT rewound here: this call's partial tiles are in it)
         for (int j = 0; j < nj; ++j) {   // (plain: one job, the caller's own pointers)
             RJob q = {};
-            q.fold = g_wg_fold != nullptr;
+            q.fold = fold != nullptr;
             q.part = part + (size_t)j * (splits / nj) * n, q.part_b = q.fold ? part_b + (size_t)j * (splits_b / nj) * nb : part_b;
-            q.gw = nj > 1 ? g_wg_fold->gw[j] : gw, q.gb = q.fold ? nullptr : gb;
+            q.gw = nj > 1 ? fold->gw[j] : gw, q.gb = q.fold ? nullptr : gb;
             q.n = n, q.nb = nb, q.splits = splits / nj, q.splits_b = splits_b / nj;
-            if (q.fold) q.R = (int)(n / nb), q.Co = nb, q.f = g_wg_fold->f[j];
+            if (q.fold) q.R = (int)(n / nb), q.Co = nb, q.f = fold->f[j];
             ar->jobs->push_back(q);
         }
         if ((long long)(ar->used * sizeof(float)) > (ar->defer_mb << 20)) {
@@ -662,9 +661,9 @@ int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_
         return 0;
     }
     const int LS = reduce_ls(splits / nj);
-    if (g_wg_fold) {
+    if (fold) {
         hipLaunchKernelGGL(conv_wgrad_reduce_bn_kernel, dim3(nb, nj), dim3(256), 0, st, part, gw, (int)(n / nb), nb, part_b,
-                           splits / nj, splits_b / nj, accumulate, LS, *g_wg_fold);
+                           splits / nj, splits_b / nj, accumulate, LS, *fold);
         LSN_HIP(hipGetLastError());
         return 0;
     }
@@ -720,51 +719,94 @@ static int wgrad_flush(Arena *ar)
     return 0;
 }
 
-// Returns 1 when the shape is not served here (more than nine taps, C % 4 != 0, 64-bit offsets): the caller keeps the
-// general kernel of dcn.hip.
-int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
-                  int dil, int accumulate, hipStream_t st)
+// The patch kernel on a call that conv_wgrad_route.h sent here (CW_PATCH, or CW_PATCH_JOBS with the jobs as levels)
+static int conv_wgrad_patch(const ConvWgradCall &c, hipStream_t st)
 {
-    // 3x3 / stride 1 / dilation 1 and 1x1 (any stride) run here.  (A strided 3x3 needs a 3 x 33 patch: one workgroup per
-    // CU and 2-way bank-conflicted tr-reads -- the general kernel of dcn.hip was faster.)
-    const bool k33 = kh == 3 && kw == 3 && stride == 1 && dil == 1, k11 = kh == 1 && kw == 1;
-    if (n < 1 || n > CV_MAXLV || !(k33 || k11) || C % 4 != 0) return 1;
+    const ConvWgradShape &s = c.s;
+    LSN_CHECK(cw_patch_ok(s), "conv2d backward-weight: not a shape of the patch kernel");
     WgArgs a = {};
     int seg = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < s.n; ++i) {
         WgLvl &L = a.lv[i];
-        const int B = lv[i].B, H = lv[i].H, W = lv[i].W;
-        if (!lv[i].x || !lv[i].grad_out || B <= 0 || H <= 0 || W <= 0) return 1;
-        const int Ho = conv_out_size(H, kh, stride, pad, dil), Wo = conv_out_size(W, kw, stride, pad, dil);
-        if (Ho <= 0 || Wo <= 0) return 1;
-        if ((int64_t)B * H * W * C * 4 >= ((int64_t)1 << 31) || (int64_t)B * Ho * Wo * Co * 4 >= ((int64_t)1 << 31)) return 1;
-        L.x = lv[i].x, L.go = lv[i].grad_out, L.B = B, L.H = H, L.W = W, L.Ho = Ho, L.Wo = Wo;
-        L.nsx = cdiv(Wo, 16);
+        L.x = c.x[i], L.go = c.go[i], L.B = s.lv[i].B, L.H = s.lv[i].H, L.W = s.lv[i].W, L.Ho = s.lv[i].Ho, L.Wo = s.lv[i].Wo;
+        L.nsx = cdiv(L.Wo, 16);
         L.seg0 = seg;
-        seg += B * Ho * L.nsx;
+        seg += L.B * L.Ho * L.nsx;
     }
-    a.nlv = n, a.nseg = seg;
-    a.C = C, a.Co = Co, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.dil = dil;
-    a.cstep = kw == 1 ? stride : 1;
-    a.PW = kw == 1 ? 16 : 15 * stride + (kw - 1) * dil + 1;
-    if (kh * a.PW > 99) return 1;
-    // (the narrow 3x3 form's 4 x 1 wave layout spills registers with one product per tap -- tools/kernel_resources.sh: 256
-    // VGPRs + 7 .. 9 spilled -- so LSN_MATH_BF16 leaves those layers to the general kernel of dcn.hip)
-    if (kh * kw == 9 && Co <= 32 && conv_np() == 1) return 1;
-    double px = 0, in_el = 0;
-    for (int i = 0; i < n; ++i) px += (double)a.lv[i].B * a.lv[i].Ho * a.lv[i].Wo, in_el += (double)a.lv[i].B * a.lv[i].H * a.lv[i].W * C;
-    ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * Co * C * kh * kw, 4.0 * (in_el + px * Co + (double)Co * kh * kw * C), st);
-    if (kh * kw == 1) {   // one tap: 32 .. 64 channels per wave on either side, by the layer's width
+    a.nlv = s.n, a.nseg = seg;
+    a.C = s.C, a.Co = s.Co, a.kh = s.kh, a.kw = s.kw, a.stride = s.stride, a.pad = c.pad, a.dil = s.dil;
+    a.cstep = s.kw == 1 ? s.stride : 1;
+    a.PW = s.kw == 1 ? 16 : 15 * s.stride + (s.kw - 1) * s.dil + 1;
+    static_assert(3 * (15 + 2 + 1) == 54 && 1 * 16 == 16, "the patches of the two geometries are the PMAX of their configurations");
+    if (s.kh * s.kw == 1) {   // one tap: 32 .. 64 channels per wave on either side, by the layer's width
         // (round-4 sweep, profiles/r4_wgrad_tiles.txt: forcing any one of the four tiles on every layer loses to this
         // width rule by 0 .. 25 %)
-        if (C <= 64)
-            return Co <= 64 ? launch_wgrad_cfg<1, 1, 1, 2, 2, 16, false>(a, gw, gb, accumulate, st)
-                            : launch_wgrad_cfg<1, 2, 1, 2, 2, 16, false>(a, gw, gb, accumulate, st);
-        return Co <= 64 ? launch_wgrad_cfg<2, 1, 1, 2, 2, 16, false>(a, gw, gb, accumulate, st)
-                        : launch_wgrad_cfg<2, 2, 1, 2, 2, 16, false>(a, gw, gb, accumulate, st);
+        if (s.C <= 64)
+            return s.Co <= 64 ? launch_wgrad_cfg<1, 1, 1, 2, 2, 16, false>(a, c, st) : launch_wgrad_cfg<1, 2, 1, 2, 2, 16, false>(a, c, st);
+        return s.Co <= 64 ? launch_wgrad_cfg<2, 1, 1, 2, 2, 16, false>(a, c, st) : launch_wgrad_cfg<2, 2, 1, 2, 2, 16, false>(a, c, st);
     }
-    if (Co <= 32) return launch_wgrad_cfg<1, 1, 9, 4, 1, 54, true>(a, gw, gb, accumulate, st);
-    return launch_wgrad_cfg<1, 1, 9, 2, 2, 54, false>(a, gw, gb, accumulate, st);
+    if (s.Co <= 32) return launch_wgrad_cfg<1, 1, 9, 4, 1, 54, true>(a, c, st);
+    return launch_wgrad_cfg<1, 1, 9, 2, 2, 54, false>(a, c, st);
+}
+
+// The one description of a weight-gradient call: arguments checked, output sizes and pixel counts filled in, and what the
+// route depends on beside the shape (pointer alignment, math mode, debug word) read here, once.
+static int conv_wgrad_call(ConvWgradCall &c, int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw,
+                           int stride, int pad, int dil, int accumulate, const WgFoldJobs *fold)
+{
+    if (fold && ((size_t)kh * kw * C) % 4 != 0)
+        return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight (folded norm): kh * kw * C %% 4 != 0");
+    LSN_CHECK(C > 0 && Co > 0 && kh > 0 && kw > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d backward-weight: bad shape");
+    LSN_CHECK(n >= 1 && n <= CW_MAXLV && lv && gw, "conv2d backward-weight: bad arguments");
+    ConvWgradShape &s = c.s;
+    s.aligned16 = true;
+    for (int i = 0; i < n; ++i) {
+        ConvWgradLevel &L = s.lv[i];
+        L.B = lv[i].B, L.H = lv[i].H, L.W = lv[i].W;
+        LSN_CHECK(lv[i].x && lv[i].grad_out && L.B > 0 && L.H > 0 && L.W > 0, "conv2d backward-weight: bad level %d", i);
+        L.Ho = conv_out(L.H, kh, stride, pad, dil), L.Wo = conv_out(L.W, kw, stride, pad, dil);
+        LSN_CHECK(L.Ho > 0 && L.Wo > 0, "conv2d backward-weight: output size is too small");
+        if ((int64_t)L.B * L.H * L.W * C >= ((int64_t)1 << 31) || (int64_t)L.B * L.Ho * L.Wo * Co >= ((int64_t)1 << 31))
+            return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight: tensor too large for 32-bit indexing");
+        L.P = L.B * L.Ho * L.Wo;
+        c.x[i] = lv[i].x, c.go[i] = lv[i].grad_out;
+        s.aligned16 = s.aligned16 && ((reinterpret_cast<uintptr_t>(c.x[i]) | reinterpret_cast<uintptr_t>(c.go[i])) & 15) == 0;
+    }
+    s.n = n, s.C = C, s.Co = Co, s.kh = kh, s.kw = kw, s.stride = stride, s.dil = dil;
+    s.np = math_np(), s.npl = split_npl(s.np), s.general_gemms = general_gemms_only(), s.fold_jobs = fold ? fold->njobs : 0;
+    c.pad = pad, c.accumulate = accumulate ? 1 : 0, c.gw = gw, c.gb = gb, c.fold = fold;
+    return 0;
+}
+
+// Weight gradient of a dense convolution, summed over the levels (input maps that share the weight): validate, route, launch.
+// With a fold the levels are its jobs, gw / gb job 0's grad_w / grad_beta: grad_beta stands in as the bias gradient, so that the
+// main kernels write the per-channel partial sums of g, and the fold-aware reduce is the only writer of the three outputs.
+static int conv_wgrad(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
+                      int dil, int accumulate, const WgFoldJobs *fold, hipStream_t st)
+{
+    ConvWgradCall c;
+    if (int rc = conv_wgrad_call(c, n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, accumulate, fold)) return rc;
+    const ConvWgradShape &s = c.s;
+    const ConvWgradRoute route = conv_wgrad_route(s);
+    if (s.fold_jobs > 1 && route != CW_PATCH_JOBS) {   // no shared launch: every job as a call of its own
+        for (int j = 0; j < n; ++j) {
+            WgFoldJobs one = {};
+            one.f[0] = fold->f[j], one.gw[0] = fold->gw[j], one.njobs = 1;
+            if (int rc = conv_wgrad(1, &lv[j], one.gw[0], one.f[0].dbeta, C, Co, kh, kw, stride, pad, dil, accumulate, &one, st)) return rc;
+        }
+        return 0;
+    }
+    // the family's account: 2 px Co C K flops, every operand once
+    double px = 0, in_el = 0;
+    for (int i = 0; i < s.n; ++i) px += (double)s.lv[i].P, in_el += (double)s.lv[i].B * s.lv[i].H * s.lv[i].W * s.C;
+    const double K = (double)s.kh * s.kw;
+    ProfSpan prof(PROF_CONV_WGRAD, 2.0 * px * s.Co * s.C * K, 4.0 * (in_el + px * s.Co + s.Co * K * s.C), st);
+    switch (route) {
+    case CW_DENSE_MM: return conv_wgrad_dense_mm(c, st);
+    case CW_PATCH:
+    case CW_PATCH_JOBS: return conv_wgrad_patch(c, st);
+    default: return conv_wgrad_general(c, st);
+    }
 }
 
 // ---- every stale image of a step in one launch ----
@@ -860,6 +902,23 @@ int lsn_wgrad_flush(lsn_stream_t stream)
     return rc;
 }
 
+int lsn_conv2d_backward_weight_multi(int n_levels, const lsn_conv_level *levels, float *grad_w, float *grad_bias, int C,
+                                     int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
+                                     lsn_stream_t stream)
+{
+    return lsn::conv_wgrad(n_levels, levels, grad_w, grad_bias, C, Co, kh, kw, stride, pad, dil, accumulate, nullptr,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int lsn_conv2d_backward_weight(const float *x, const float *grad_out, float *grad_w, float *grad_bias, int B, int H,
+                               int W, int C, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
+                               lsn_stream_t stream)
+{
+    lsn_conv_level L = {};
+    L.x = x, L.grad_out = grad_out, L.B = B, L.H = H, L.W = W;
+    return lsn_conv2d_backward_weight_multi(1, &L, grad_w, grad_bias, C, Co, kh, kw, stride, pad, dil, accumulate, stream);
+}
+
 int lsn_conv2d_backward_weight_bn(const float *x, const float *g, const float *w, const float *bn_gamma, const float *bn_mean,
                                   const float *bn_var, float bn_eps, float *grad_w, float *grad_gamma, float *grad_beta, int B,
                                   int H, int W, int C, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
@@ -867,17 +926,8 @@ int lsn_conv2d_backward_weight_bn(const float *x, const float *g, const float *w
 {
     LSN_CHECK(x && g && w && bn_gamma && bn_mean && bn_var && grad_w && grad_gamma && grad_beta,
               "conv2d backward-weight (folded norm): NULL pointer");
-    if (((size_t)kh * kw * C) % 4 != 0)
-        return lsn::fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight (folded norm): kh * kw * C %% 4 != 0");
-    lsn::WgFoldJobs f = {};
-    f.f[0] = lsn::WgFold{w, bn_gamma, bn_mean, bn_var, grad_gamma, grad_beta, bn_eps};
-    f.gw[0] = grad_w, f.njobs = 1;
-    lsn::g_wg_fold = &f;
-    // grad_beta stands in as the bias gradient: the main kernels then write the per-channel partial sums of g, and the
-    // fold-aware reduce is the only writer of grad_w / grad_gamma / grad_beta
-    const int rc = lsn_conv2d_backward_weight(x, g, grad_w, grad_beta, B, H, W, C, Co, kh, kw, stride, pad, dil, accumulate, stream);
-    lsn::g_wg_fold = nullptr;
-    return rc;
+    const lsn_wgrad_bn_job q = {x, g, w, bn_gamma, bn_mean, bn_var, bn_eps, grad_w, grad_gamma, grad_beta};
+    return lsn_conv2d_backward_weight_bn_jobs(1, &q, B, H, W, C, Co, kh, kw, stride, pad, dil, accumulate, stream);
 }
 
 int lsn_conv2d_backward_weight_bn_jobs(int n_jobs, const lsn_wgrad_bn_job *jobs, int B, int H, int W, int C, int Co, int kh, int kw,
@@ -895,21 +945,8 @@ int lsn_conv2d_backward_weight_bn_jobs(int n_jobs, const lsn_wgrad_bn_job *jobs,
         lv[j].x = q.x, lv[j].grad_out = q.g, lv[j].B = B, lv[j].H = H, lv[j].W = W;
     }
     f.njobs = n_jobs;
-    int rc = 1;
-    if (n_jobs > 1 && ((size_t)kh * kw * C) % 4 == 0) {   // the patch kernel with the jobs as levels; 1: shape not served there
-        lsn::g_wg_fold = &f;
-        rc = lsn::conv_wgrad_mm(n_jobs, lv, jobs[0].grad_w, jobs[0].grad_beta, C, Co, kh, kw, stride, pad, dil, accumulate,
-                                reinterpret_cast<hipStream_t>(stream));
-        lsn::g_wg_fold = nullptr;
-    }
-    if (rc != 1) return rc;
-    for (int j = 0; j < n_jobs; ++j) {
-        const lsn_wgrad_bn_job &q = jobs[j];
-        if (int r = lsn_conv2d_backward_weight_bn(q.x, q.g, q.w, q.bn_gamma, q.bn_mean, q.bn_var, q.bn_eps, q.grad_w, q.grad_gamma,
-                                                  q.grad_beta, B, H, W, C, Co, kh, kw, stride, pad, dil, accumulate, stream))
-            return r;
-    }
-    return 0;
+    return lsn::conv_wgrad(n_jobs, lv, f.gw[0], f.f[0].dbeta, C, Co, kh, kw, stride, pad, dil, accumulate, &f,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 int lsn_conv2d_prepare_weights_multi(int n_items, const lsn_conv_wprep *items, lsn_stream_t stream)

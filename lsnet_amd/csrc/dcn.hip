@@ -931,9 +931,9 @@ static int wgrad_vec_bits(const DcnArgs &a)
 }
 
 // ---- weight gradient on the kernels of dcn_mm_kernels.h: grad_output in fragment order, split partial tiles ----
-// dense: a dense convolution's weight gradient (levels without offsets, no backward-data pass before this one): the
-// sampling table is built here, and the launch is accounted to the caller's family
-static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hipStream_t st, bool dense = false)
+// dense: a dense convolution's weight gradient (conv_wgrad_dense_mm: levels without offsets, no backward-data pass before this
+// one): the sampling table is built here, the launch is accounted to the caller's family, the reduce applies the call's fold
+static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hipStream_t st, const ConvWgradCall *dense = nullptr)
 {
     DcnArgs a = a_in;
     const int K = a.kh * a.kw, npl = mm_npl();
@@ -950,7 +950,7 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
     const size_t img_f = (img_bytes + 15) / 16 * 4, part_f = (size_t)S * nW, pb_f = ((size_t)nblk_s * a.Co + 3) & ~(size_t)3;
     const size_t meta_f = ((size_t)nchunks * 8 + 64 + 3) & ~(size_t)3;
     size_t tap_entries = 0;
-    if (dense) {   // (< 2^26 entries, a 2 GB table: conv_wgrad_dense_mm_ok)
+    if (dense) {   // (< 2^26 entries, a 2 GB table: cw_dense_mm_ok)
         a.gtap_rows = number_rows(a);
         tap_entries = (size_t)a.gtap_rows * K * a.dg;
     }
@@ -986,7 +986,7 @@ static int launch_wgrad_mm(const DcnArgs &a_in, int nchunks, bool accumulate, hi
                          : launch256(dcn_wgrad_mm_kernel<NP, false, true>, grid, lds, st, a, nchunks, img, (int)img_bytes, part, meta);
         }))
         return rc;
-    return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, S, nblk_s, accumulate ? 1 : 0, st);
+    return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, S, nblk_s, accumulate ? 1 : 0, dense ? dense->fold : nullptr, st);
 }
 
 // grouped weight gradient (dcn_grouped_kernels.h): pixel splits leave partial tiles, the ordered reduce adds them (or queues)
@@ -1024,7 +1024,7 @@ static int launch_wgrad_grouped(const DcnArgs &a_in, bool accumulate, hipStream_
     default: rc = launch256(dcn_wgrad_grouped_kernel<32, 9>, grid, lds, st, a, rows, per, part, part_b); break;
     }
     if (rc) return rc;
-    return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
+    return conv_wgrad_reduce(part, a.gw, nW, part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, nullptr, st);
 }
 
 // the split kernels (WG_XN_* / WG_FP32_*): ORDERED = one partial gradient per pixel split + an ordered reduce; a block that
@@ -1061,7 +1061,7 @@ static int launch_wgrad_split(const DcnArgs &a_in, const DcnRoute &r, bool accum
         });
     }
     if (rc || !ordered) return rc;
-    return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, st);
+    return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, a.Co, splits, splits, accumulate ? 1 : 0, nullptr, st);
 }
 
 static int launch_wgrad(const DcnArgs &a, const DcnRoute &r, bool accumulate, hipStream_t st)
@@ -1251,8 +1251,6 @@ static lsn_strides4 nchw_strides(int Ch, int H, int W)
     return s;
 }
 
-static int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
-
 // shape + single NCHW level for the one-to-one wrappers
 static int make_single(lsn_dcn_shape &s, lsn_dcn_level &L, int B, int C, int H, int W, int Co, int Ho, int Wo,
                        int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int group, int dg,
@@ -1289,11 +1287,44 @@ static int make_single(lsn_dcn_shape &s, lsn_dcn_level &L, int B, int C, int H, 
     return 0;
 }
 
-// weight gradient of a dense convolution through the deformable-conv weight-gradient kernel (PLAIN: no offsets), summed
-// over up to MAXLV input maps that share the weight
-template <int NP, int BMW>
-static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool accumulate, hipStream_t st)
+// ---- the weight gradient of a dense convolution on this family's kernels (conv.hip validates, routes and accounts the call) ----
+static_assert(CW_MAXLV <= MAXLV && CW_STEP_PX == WG_BP, "conv_wgrad_route.h counts the k-steps of these kernels");
+bool general_gemms_only() { return !dcn_mm_env(); }
+
+// The levels of the call as DcnArgs (no offsets: the regular grid is the sampling table); returns the 32-pixel steps
+static int conv_dcn_args(DcnArgs &a, const ConvWgradCall &c)
 {
+    const ConvWgradShape &s = c.s;
+    a = DcnArgs{};
+    int steps = 0;
+    for (int i = 0; i < s.n; ++i) {
+        Lvl &L = a.lv[i];
+        L.x = c.x[i], L.gout = c.go[i];
+        L.B = s.lv[i].B, L.H = s.lv[i].H, L.W = s.lv[i].W, L.Ho = s.lv[i].Ho, L.Wo = s.lv[i].Wo, L.P = s.lv[i].P, L.sh = L.sw = 1.f;
+        L.tile0 = steps;
+        steps += cdiv(L.P, WG_BP);
+    }
+    a.nlv = s.n;
+    a.C = s.C, a.Co = s.Co, a.kh = s.kh, a.kw = s.kw, a.stride = s.stride, a.pad = c.pad, a.dil = s.dil, a.groups = 1, a.dg = 1;
+    a.SL = s.C;
+    a.opitch = s.Co;
+    a.gw = c.gw, a.gb = c.gb;
+    return steps;
+}
+
+int conv_wgrad_dense_mm(const ConvWgradCall &c, hipStream_t st)
+{
+    LSN_CHECK(cw_dense_mm_ok(c.s) && c.s.fold_jobs <= 1, "conv2d backward-weight: not a shape of the fragment-order kernel");
+    DcnArgs a;
+    const int steps = conv_dcn_args(a, c);
+    return launch_wgrad_mm(a, steps, c.accumulate != 0, st, &c);
+}
+
+// dcn_wgrad_xn_kernel<PLAIN> (no offsets) with BMW output channels per workgroup
+template <int NP, int BMW>
+static int conv_wgrad_launch(DcnArgs a, int nsteps, const ConvWgradCall &c, hipStream_t st)
+{
+    const int C = a.C, Co = a.Co, K = a.kh * a.kw;
     const int ncc = cdiv(C, WG_BN), ncol = K * ncc, nz = cdiv(Co, BMW);
     int splits = wgrad_splits(ncol * nz, BMW == 256 ? 2 : 3);   // resident blocks per CU: registers (246 / 142 VGPRs)
     if (splits > nsteps) splits = nsteps;
@@ -1302,102 +1333,32 @@ static int conv_wgrad_launch(DcnArgs a, int nsteps, int C, int Co, int K, bool a
     // one partial gradient per pixel split + an ordered reduce (deterministic) where the sizes allow; else fp32 atomics
     const size_t nW = (size_t)Co * K * C;
     const bool ordered = nW % 4 == 0 && (size_t)splits * (nW + Co) * sizeof(float) <= ((size_t)256 << 20);
-    if (!ordered && conv_wgrad_fold_pending())
+    if (!ordered && c.fold)
         return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight (folded norm): the gradient is too large for the ordered reduce");
     if (ordered) {
         float *base = nullptr;
         if (int rc = wgrad_part_buffer((size_t)splits * (nW + Co) + 16, &base, st)) return rc;
         a.wg_part = base;
         a.wg_part_b = a.gb ? base + (((size_t)splits * nW + 3) & ~(size_t)3) : nullptr;
-    } else if (!accumulate) {
+    } else if (!c.accumulate) {
         LSN_HIP(hipMemsetAsync(a.gw, 0, sizeof(float) * nW, st));
         if (a.gb) LSN_HIP(hipMemsetAsync(a.gb, 0, sizeof(float) * (size_t)Co, st));
     }
     if (int rc = launch256(dcn_wgrad_xn_kernel<true, NP, BMW>, dim3(ncol, splits, nz), wgrad_xn_lds_bytes<NP, BMW>(), st, a, nsteps)) return rc;
-    if (ordered) return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, Co, splits, splits, accumulate ? 1 : 0, st);
+    if (ordered) return conv_wgrad_reduce(a.wg_part, a.gw, nW, a.wg_part_b, a.gb, Co, splits, splits, c.accumulate, c.fold, st);
     return 0;
 }
 
-// The levels of a dense convolution as DcnArgs (no offsets: the regular grid is the sampling table), 32-pixel steps in *steps
-static int conv_levels(DcnArgs &a, int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
-                       int pad, int dil, int *steps)
+int conv_wgrad_general(const ConvWgradCall &c, hipStream_t st)
 {
-    LSN_CHECK(n >= 1 && n <= MAXLV && lv && gw, "conv2d backward-weight: bad arguments");
-    *steps = 0;
-    for (int i = 0; i < n; ++i) {
-        Lvl &L = a.lv[i];
-        const int B = lv[i].B, H = lv[i].H, W = lv[i].W;
-        LSN_CHECK(lv[i].x && lv[i].grad_out && B > 0 && H > 0 && W > 0, "conv2d backward-weight: bad level %d", i);
-        const int Ho = conv_out(H, kh, stride, pad, dil), Wo = conv_out(W, kw, stride, pad, dil);
-        LSN_CHECK(Ho > 0 && Wo > 0, "conv2d backward-weight: output size is too small");
-        if (!fits_i32((int64_t)B * H * W * C) || !fits_i32((int64_t)B * Ho * Wo * Co))
-            return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-weight: tensor too large for 32-bit indexing");
-        L.x = lv[i].x, L.gout = lv[i].grad_out, L.off = nullptr, L.msk = nullptr;
-        L.B = B, L.H = H, L.W = W, L.Ho = Ho, L.Wo = Wo, L.P = B * Ho * Wo, L.sh = L.sw = 1.f;
-        L.tile0 = *steps;
-        *steps += cdiv(L.P, WG_BP);
-    }
-    a.nlv = n;
-    a.C = C, a.Co = Co, a.kh = kh, a.kw = kw, a.stride = stride, a.pad = pad, a.dil = dil, a.groups = 1, a.dg = 1;
-    a.SL = C;
-    a.opitch = Co;
-    a.gw = gw, a.gb = gb;
-    return 0;
-}
-
-static ProfSpan conv_wgrad_span(const DcnArgs &a, hipStream_t st)
-{
-    double px = 0, in_el = 0;
-    for (int i = 0; i < a.nlv; ++i) px += (double)a.lv[i].P, in_el += (double)in_elems(a, i);
-    const double K = (double)a.kh * a.kw;
-    return ProfSpan(PROF_CONV_WGRAD, 2.0 * px * a.Co * a.C * K, 4.0 * (in_el + px * a.Co + a.Co * K * a.C), st);
-}
-
-// Whether the weight gradient of a dense convolution goes through dcn_wgrad_mm_kernel<NP, DENSE> (grad_output pre-split once
-// into MFMA fragment order, the regular grid as the sampling table): the shape is served (256 | Co, 64 | C, 16-byte aligned
-// tensors at 32-bit byte offsets, a split-bf16 math mode) and is not faster on the patch kernel of conv_wgrad_kernels.h.
-// Measured on the layer shapes of the benchmark step (tools/ubench/wgrad_ab.hip, profiles/r3_wgrad_ab.txt; batch 2): 3x3 at >= 4096
-// output pixels 84 vs 96 us (layer 3), 262 vs 272 (FPN P3), 320 vs 380 (five head levels in one launch); 1x1 from >= 1024
-// channels to >= 512: 75 vs 89, 53 vs 56; strided 1x1 from >= 512 channels: 83 vs 89, 78 vs 89.  Slower on the 1x1 layers
-// with few input channels and many pixels (76 vs 52 us on 128 -> 512 at 100 x 168), which stay where they were.
-static bool conv_wgrad_dense_mm_ok(const DcnArgs &a, int chunks)
-{
-    if (a.Co % 256 != 0 || a.C % 64 != 0) return false;
-    int64_t opx = 0;   // output pixels
-    for (int i = 0; i < a.nlv; ++i) {
-        opx += a.lv[i].P;
-        if (((reinterpret_cast<uintptr_t>(a.lv[i].x) | reinterpret_cast<uintptr_t>(a.lv[i].gout)) & 15) != 0) return false;   // 16-byte loads
-    }
-    // (all of them measured at >= 2100 output pixels; smaller launches stay where they were)
-    const bool win = a.kh * a.kw >= 9 ? opx >= 4096 : opx >= 2048 && ((a.C >= 1024 && a.Co >= 512) || (a.stride >= 2 && a.C >= 512));
-    if (!win || !mm_common_ok(a) || chunks < 8) return false;
-    return wgrad_mm_image_ok(a, chunks) && opx * a.kh * a.kw < ((int64_t)1 << 26);   // (the tap table: 2 GB)
-}
-
-// weight gradient of a dense convolution, summed over up to MAXLV input maps that share the weight
-static int conv_wgrad_xn(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride,
-                         int pad, int dil, bool accumulate, hipStream_t st)
-{
-    DcnArgs a = {};
-    int steps = 0;
-    const int bad = conv_levels(a, n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, &steps);
-    if (!bad && conv_wgrad_dense_mm_ok(a, steps)) {   // wide layers: the fragment-order kernel of the deformable family
-        ProfSpan prof = conv_wgrad_span(a, st);
-        return launch_wgrad_mm(a, steps, accumulate, st, true);
-    }
-    {   // the patch kernel of conv_wgrad_kernels.h serves up to nine taps (1: not served -- conv.hip); anything else stays here
-        const int rc = conv_wgrad_mm(n, lv, gw, gb, C, Co, kh, kw, stride, pad, dil, accumulate ? 1 : 0, st);
-        if (rc != 1) return rc;
-    }
-    if (bad) return bad;
+    LSN_CHECK(c.s.fold_jobs <= 1, "conv2d backward-weight: folded-norm jobs share a launch on the patch kernel only");
+    DcnArgs a;
+    const int steps = conv_dcn_args(a, c);
     a.wg_vec = wgrad_vec_bits(a);
-    ProfSpan prof = conv_wgrad_span(a, st);
     // exact-mode callers get the fp32-equivalent split: there is no fp32-MFMA dense wgrad
-    const int np = math_np() == 0 ? 6 : math_np();
-    return split_dispatch(np, [&](auto npc) {
+    return split_dispatch(c.s.np == 0 ? 6 : c.s.np, [&](auto npc) {
         constexpr int NP = decltype(npc)::value;
-        return Co <= 64 ? conv_wgrad_launch<NP, 64>(a, steps, C, Co, kh * kw, accumulate, st)
-                        : conv_wgrad_launch<NP, 256>(a, steps, C, Co, kh * kw, accumulate, st);
+        return a.Co <= 64 ? conv_wgrad_launch<NP, 64>(a, steps, c, st) : conv_wgrad_launch<NP, 256>(a, steps, c, st);
     });
 }
 
@@ -1495,24 +1456,6 @@ int lsn_dcn_anchor_lists(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn
                        reinterpret_cast<const GEntry *>(w + pl.o_ent), sample_anchor, list_start, list_sample);
     LSN_HIP(hipGetLastError());
     return 0;
-}
-
-int lsn_conv2d_backward_weight_multi(int n_levels, const lsn_conv_level *levels, float *grad_w, float *grad_bias, int C,
-                                     int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                                     lsn_stream_t stream)
-{
-    LSN_CHECK(C > 0 && Co > 0 && kh > 0 && kw > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d backward-weight: bad shape");
-    return conv_wgrad_xn(n_levels, levels, grad_w, grad_bias, C, Co, kh, kw, stride, pad, dil, accumulate != 0,
-                         reinterpret_cast<hipStream_t>(stream));
-}
-
-int lsn_conv2d_backward_weight(const float *x, const float *grad_out, float *grad_w, float *grad_bias, int B, int H,
-                               int W, int C, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                               lsn_stream_t stream)
-{
-    lsn_conv_level L = {};
-    L.x = x, L.grad_out = grad_out, L.B = B, L.H = H, L.W = W;
-    return lsn_conv2d_backward_weight_multi(1, &L, grad_w, grad_bias, C, Co, kh, kw, stride, pad, dil, accumulate, stream);
 }
 
 int lsn_dcn_forward(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, const float *weight,

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "conv_wgrad_route.h"
 #include "per_stream.h"
 
 namespace lsn {
@@ -52,15 +53,30 @@ int arena_get(hipStream_t st, Arena **ar);   // ... created when it is not there
 // arena -- deferral is off for the stream from now on, the caller takes the scratch block
 int arena_alloc(Arena *ar, size_t floats, float **p, int (*flush)(Arena *));
 
+// One validated weight-gradient call of a dense convolution (conv.hip conv_wgrad_call builds it, conv_wgrad_route.h routes it)
+struct WgFoldJobs;   // the folded BatchNorm(s) of the call (conv_wgrad_kernels.h) -- carried here, never looked into
+struct ConvWgradCall {
+    ConvWgradShape s;   // levels with Ho, Wo and pixel counts; C, Co, kh, kw, stride, dil; what else the route looks at
+    const float *x[CW_MAXLV], *go[CW_MAXLV];
+    int pad, accumulate;
+    float *gw, *gb;
+    const WgFoldJobs *fold;   // nullptr: a plain call
+};
+
 // ---- conv.hip, for dcn.hip ----
 // partial tiles of ONE weight-gradient call: from the arena while the stream defers, else the scratch block
 int wgrad_part_buffer(size_t floats, float **p, hipStream_t st);
 int conv_mm_rows(int n, const float *const *x, float *const *out, const int *rows, int Cr, int xpitch, int N,
                  const unsigned short *wf, hipStream_t st);
-int conv_wgrad_mm(int n, const lsn_conv_level *lv, float *gw, float *gb, int C, int Co, int kh, int kw, int stride, int pad,
-                  int dil, int accumulate, hipStream_t st);
+// gw (+)= sum of `splits` partial gradients of n floats (n % 4 == 0), gb (+)= sum of splits_b partial rows of nb; launched, or
+// queued while the stream defers.  fold: the reduce also applies the norm's scale and forms grad_gamma / grad_beta
 int conv_wgrad_reduce(const float *part, float *gw, size_t n, const float *part_b, float *gb, int nb, int splits, int splits_b,
-                      int accumulate, hipStream_t st);
-bool conv_wgrad_fold_pending();   // inside lsn_conv2d_backward_weight_bn: the reduce applies the folded norm
+                      int accumulate, const WgFoldJobs *fold, hipStream_t st);
+
+// ---- dcn.hip, for conv.hip: the two routes of a dense weight gradient on the deformable family's kernels ----
+bool general_gemms_only();   // LSN_DBG_GENERAL_GEMMS is set
+int conv_wgrad_dense_mm(const ConvWgradCall &c, hipStream_t st);   // CW_DENSE_MM: the fragment-order kernel with the tap table
+// CW_GENERAL: the PLAIN split kernel with its ordered reduce (fp32 atomics above 256 MB of partial tiles; refused under a fold)
+int conv_wgrad_general(const ConvWgradCall &c, hipStream_t st);
 
 }  // namespace lsn

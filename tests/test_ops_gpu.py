@@ -824,7 +824,7 @@ CONV_CASES = [
     (1, 208, 27, 3, 2, 1, 1, 6, 8, True),         # ... at the Res2Net per-scale widths
     (1, 104, 27, 3, 2, 1, 1, 12, 16, True),
     (1, 52, 27, 3, 2, 1, 1, 24, 32, True),
-    # weight gradients on the deformable family's fragment-order kernel (csrc/dcn.hip conv_wgrad_dense_mm_ok: 256 | Co, 64 | C and
+    # weight gradients on the deformable family's fragment-order kernel (csrc/conv_wgrad_route.h cw_dense_mm_ok: 256 | Co, 64 | C and
     # 3x3 at >= 4096 output pixels / wide 1x1 at >= 2048 / strided 1x1 from >= 512 channels) -- the rows above stay below
     # its thresholds, and a pitch the dense caller left unset went unnoticed in round 4 until the benchmark's loss moved
     (2, 64, 256, 3, 1, 1, 1, 48, 50, True),

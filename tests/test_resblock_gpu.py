@@ -2,7 +2,9 @@
 and a whole stage (ResLayer of three bottlenecks: projection shortcut, strided conv2, pregate flags between the blocks)
 against autograd over the plain modules in fp64 on the host -- output, input gradient and every parameter gradient,
 zero and tiny gammas included."""
+import contextlib
 import copy
+import functools
 
 import pytest
 import torch
@@ -148,3 +150,121 @@ def test_identical_blocks_batched_weight_gradients():
     for k, p in layer.named_parameters():
         assert _err(p.grad - seed[k], pr[k].grad) < 2e-5, (k, _err(p.grad - seed[k], pr[k].grad))
     assert _err(xd.grad, xr.grad) < 2e-5
+
+
+# ---- the folded-norm weight gradient where the dense route takes the fragment-order kernel of the deformable family ----
+# (3x3 at >= 4096 output pixels, strided 1x1 from >= 512 channels at >= 2048: csrc/conv_wgrad_route.h; the cases above stay below)
+MM_SHAPES = [(64, 256, 3, 1, 64), (512, 256, 1, 2, 92)]
+
+
+@contextlib.contextmanager
+def _bf16x6():
+    from lsnet_amd import _lib
+    old = _lib.get_math_mode()
+    try:
+        _lib.set_math_mode('bf16x6')
+        yield
+    finally:
+        _lib.set_math_mode(old)
+
+
+@functools.lru_cache(maxsize=None)
+def _mm_case(C, Co, k, s, HW, seed=3):
+    """conv + eval-mode BatchNorm (gammas 0 and 1e-6 among them), x and g on the device, and the parameter gradients in fp64:
+    built once per shape, shared by the tests below, never written."""
+    from lsnet_amd.ops import conv as K
+    dev = torch.device('cuda:0')
+    torch.manual_seed(seed)
+    conv = K.Conv2d(C, Co, k, stride=s, padding=k // 2, bias=False).to(dev).to(memory_format=CL)
+    bn = torch.nn.BatchNorm2d(Co).to(dev).eval()
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(Co) + 0.5)
+        bn.weight[:4] = 0.0
+        bn.weight[4:8] = 1e-6
+        bn.bias.copy_(torch.randn(Co) * 0.3)
+        bn.running_mean.copy_(torch.randn(Co) * 0.5)
+        bn.running_var.copy_(torch.rand(Co) + 0.5)
+    Ho = (HW + 2 * (k // 2) - k) // s + 1
+    x = torch.randn(1, C, HW, HW, device=dev).contiguous(memory_format=CL)
+    g = torch.randn(1, Co, Ho, Ho, device=dev).contiguous(memory_format=CL)
+    d = lambda t: t.detach().double().cpu()
+    ref = TorchPrims.wgrad_bn(d(x), d(g), copy.deepcopy(conv).double().cpu().weight, copy.deepcopy(bn).double().cpu(), s, k // 2, 1)
+    return conv, bn, x, g, tuple(r.detach() for r in ref)
+
+
+@pytest.mark.parametrize('C,Co,k,s,HW', MM_SHAPES)
+def test_wgrad_bn_on_the_fragment_order_route(C, Co, k, s, HW):
+    """wgrad_bn at the two smallest shapes of the fragment-order route -- 4096 pixels of a 3x3, 2116 of a strided 1x1 -- where the
+    bias rows come in another split count than the gradient tiles (splits_b != splits) and feed the folded-norm reduce."""
+    from lsnet_amd.ops import conv as K
+    conv, bn, x, g, ref = _mm_case(C, Co, k, s, HW)
+    with _bf16x6():
+        got = K.wgrad_bn(x, g, conv.weight, bn, s, k // 2, 1)
+    errs = {n: _err(a, r) for a, r, n in zip(got, ref, ('gw', 'dgamma', 'dbeta'))}
+    print(errs)
+    assert all(e < 5e-6 for e in errs.values()), errs
+
+
+def test_wgrad_bn_accumulates_plain_and_deferred():
+    """lsn_conv2d_backward_weight_bn(accumulate = 1) twice onto the same non-zero buffers, on the fragment-order route: run
+    plainly, and between lsn_wgrad_defer(64) and lsn_wgrad_defer(0), where the fold job with its own bias split count waits in
+    the queue and the second call finds it there (`clash`) -- the same bits both times, and start + 2 x the fp64 gradient."""
+    from lsnet_amd import _lib
+    C, Co, k, s, HW = MM_SHAPES[0]
+    conv, bn, x, g, ref = _mm_case(C, Co, k, s, HW)
+    lib = _lib.load()
+
+    def run(defer):
+        torch.manual_seed(11)
+        start = [torch.randn_like(conv.weight), torch.randn_like(bn.weight), torch.randn_like(bn.bias)]
+        bufs = [t.clone() for t in start]
+        assert bufs[0].stride() == conv.weight.stride()
+        if defer:
+            _lib.wgrad_defer(64)
+        try:
+            for _ in range(2):
+                _lib.check(lib.lsn_conv2d_backward_weight_bn(
+                    x.data_ptr(), g.data_ptr(), conv.weight.data_ptr(), bn.weight.data_ptr(), bn.running_mean.data_ptr(),
+                    bn.running_var.data_ptr(), float(bn.eps), bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), 1, HW, HW,
+                    C, Co, k, k, s, k // 2, 1, 1, _lib.stream()))
+        finally:
+            if defer:
+                _lib.wgrad_defer(0)
+        torch.cuda.synchronize()
+        return start, bufs
+
+    with _bf16x6():
+        start, plain = run(False)
+        start_d, deferred = run(True)
+    for a, b, n in zip(plain, deferred, ('gw', 'dgamma', 'dbeta')):
+        assert torch.equal(a, b), n
+    errs = {n: _err(a.double() - s0.double(), 2 * r) for a, s0, r, n in zip(plain, start, ref, ('gw', 'dgamma', 'dbeta'))}
+    print(errs)
+    assert all(torch.equal(a, b) for a, b in zip(start, start_d))
+    assert all(e < 5e-6 for e in errs.values()), errs
+
+
+def test_wgrad_bn_jobs_stay_on_the_patch_kernel():
+    """Two jobs of the shape whose single call takes the fragment-order kernel: lsn_conv2d_backward_weight_bn_jobs runs them as
+    levels of the patch kernel, into sinks, and agrees with the two single calls up to the summation order over pixels."""
+    from lsnet_amd.ops import conv as K
+    from lsnet_amd.ops import grad_sink
+    C, Co, k, s, HW = MM_SHAPES[0]
+    cases = [_mm_case(C, Co, k, s, HW), _mm_case(C, Co, k, s, HW, seed=5)]
+    params = [p for conv, bn, _, _, _ in cases for p in (conv.weight, bn.weight, bn.bias)]
+    with _bf16x6():
+        single = [K.wgrad_bn(x, g, conv.weight, bn, s, k // 2, 1) for conv, bn, x, g, _ in cases]
+        try:
+            for p in params:
+                p.grad = torch.zeros_like(p)
+                grad_sink.register(p, p.grad)
+            K.wgrad_bn_jobs([(x, g, conv.weight, bn) for conv, bn, x, g, _ in cases], s, k // 2, 1)
+            torch.cuda.synchronize()
+            sunk = [p.grad for p in params]
+        finally:
+            for p in params:
+                grad_sink.unregister(p)
+                p.grad = None
+    errs = [_err(a, r) for a, r in zip(sunk, [t for one in single for t in one])]
+    print(errs)
+    assert all(e < 5e-6 for e in errs), errs
