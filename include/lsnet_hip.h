@@ -731,6 +731,22 @@ int lsn_cross_iou_rows_backward(int kind, const float *pred, const float *target
                                 const float *bbox_gt, const float *vs, const float *weight, const float *grad_rows, int64_t n,
                                 int ncomp, int sub, float alpha, float eps, float *grad_pred, lsn_stream_t stream);
 
+/* The whole regression stage of LSHead.loss_single for n points of the segm (kind 1 = polygon) and pose (kind 2 = keypoint)
+ * tasks (lsnet_head.py:402-454, 1103-1270), as lsn_cross_iou_bbox_stage_* is for the bbox task: pred_raw (n, ncomp) in stride
+ * units, ncomp = 4 (nv + 1), 16-byte aligned; gt_pts (n, ncomp / 2): the nv landmarks and the centre as (x, y) in pixels,
+ * 8-byte aligned; anchor3 (n, 3) = (x, y, stride); bbox_gt (n, 4) in pixels (polygon; may be NULL for keypoint); vs (n, nv)
+ * (keypoint; may be NULL for polygon); weight (n), required: 0 for points without an object.  Scaling to pixels,
+ * normalisation by base_scale * stride, target and active-half construction and the row of lsn_cross_iou_rows_* happen on a
+ * tile of 64 rows staged in LDS, every global access of pred_raw, gt_pts and grad_raw coalesced.  forward: loss_rows (n) =
+ * weight x row loss.  backward: grad_raw (n, ncomp), OVERWRITTEN, = grad_rows x weight x d row / d pred_raw.
+ * LSN_ERR_UNSUPPORTED when a tile of ncomp-wide rows exceeds 64 KiB of LDS (polygon: ncomp > 164, keypoint: ncomp > 140). */
+int lsn_cross_iou_stage_forward(int kind, const float *pred_raw, const float *gt_pts, const float *anchor3, const float *bbox_gt,
+                                const float *vs, const float *weight, int64_t n, int ncomp, int sub, float base_scale,
+                                float alpha, float eps, float *loss_rows, lsn_stream_t stream);
+int lsn_cross_iou_stage_backward(int kind, const float *pred_raw, const float *gt_pts, const float *anchor3, const float *bbox_gt,
+                                 const float *vs, const float *weight, const float *grad_rows, int64_t n, int ncomp, int sub,
+                                 float base_scale, float alpha, float eps, float *grad_raw, lsn_stream_t stream);
+
 /* ---- pooling and resampling (csrc/pool.hip; index, tie and divisor rules in csrc/pool_rows.h) ------------------------
  * What the reference gets from the framework around its convolutions: the ResNet stem's MaxPool2d(3, 2, 1)
  * (mmdet/models/backbones/resnet.py:567), the FPN's nearest upsample + add and its stride-2 extra levels

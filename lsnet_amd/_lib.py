@@ -226,6 +226,8 @@ def _signatures():
         'lsn_cross_iou_bbox_stage_backward': (i, [p] * 6 + [q, f, f, f, p, p]),
         'lsn_cross_iou_rows_forward': (i, [i] + [p] * 7 + [q, i, i, f, f, p, p]),
         'lsn_cross_iou_rows_backward': (i, [i] + [p] * 8 + [q, i, i, f, f, p, p]),
+        'lsn_cross_iou_stage_forward': (i, [i] + [p] * 6 + [q, i, i, f, f, f, p, p]),
+        'lsn_cross_iou_stage_backward': (i, [i] + [p] * 7 + [q, i, i, f, f, f, p, p]),
         'lsn_pool_output_size': (i, [i] * 5),
         'lsn_max_pool2d_forward': (i, [p, i, p, i, p] + [i] * 8 + [p]),
         'lsn_max_pool2d_backward': (i, [p, i, p, p] + [i] * 9 + [p]),

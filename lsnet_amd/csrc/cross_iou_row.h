@@ -15,8 +15,10 @@
 
 #if defined(__HIPCC__)
 #define LSN_HD __host__ __device__ __forceinline__
+#define LSN_HDM __host__ __device__ __forceinline__
 #else
 #define LSN_HD static inline
+#define LSN_HDM inline
 #endif
 
 struct CrossIouRow {
@@ -121,6 +123,9 @@ LSN_HD void cross_iou_bbox_stage_row(const float *pred_raw, const float *gt_pts,
 // bbox row) and :80-94 (keypoint: per (neg, pos) pair the ratio sum(min) / sum(max clamped at eps), weighted by the
 // keypoint's visibility, the centre pairs always counted; no box terms).  M = 4 (nv + 1) components per row; nothing
 // is copied into local arrays (M = 148 / 72): the row is read where it lies and the gradient written where it goes.
+// The formulas are written once over a source `s` of the row -- s.p(c): the prediction, s.tt(c): the completed target of
+// component c -- which the rows (CiouPlainSrc: p, t, active as stored) and the stage rows (CiouStageSrc: raw prediction,
+// ground-truth points and anchor; the target is derived where it is needed) both instantiate.
 #define LSN_CIOU_MAXSUB 16
 
 // completed target of component c (the inactive half of a pair is alpha x the active half)
@@ -135,30 +140,77 @@ LSN_HD float ciou_tt(const float *t, const unsigned char *active, int c, float a
 LSN_HD float ciou_dmin(float p, float t) { return p < t ? 1.f : (p == t ? .5f : 0.f); }
 LSN_HD float ciou_dmax(float p, float t) { return p > t ? 1.f : (p == t ? .5f : 0.f); }
 
-// returns the unweighted loss; grad (M floats, may be NULL) receives d loss / d pred
-LSN_HD float cross_iou_polygon_row(const float *p, const float *t, const unsigned char *active, const float *anchor,
-                                   const float *gt, int nv, int sub, float alpha, float eps, float *grad)
+// a row as the loss module hands it over: prediction, target and active-half mask, M values each
+struct CiouPlainSrc {
+    const float *pred, *target;
+    const unsigned char *active;
+    float alpha;
+    LSN_HDM float p(int c) const { return pred[c]; }
+    LSN_HDM float tt(int c) const { return ciou_tt(target, active, c, alpha); }
+};
+
+// A row of a regression stage of LSHead.loss_levels is made of two kinds of values (LSHead._gt_reg, lsnet_head.py:402-454):
+//   ciou_stage_p: the prediction in stride units -> pixels -> normalised by norm = base_scale * stride;
+//   ciou_stage_d: the signed normalised offset of a ground-truth coordinate from the anchor, d = gt - anchor; `d >= 0`
+//                 selects the positive half of the pair [y_up, y_down] / [x_left, x_right], |d| / norm is that half's target
+//                 (0 in a row without an object, where the selection then decides nothing: both halves complete to 0);
+// and its gradient goes back through ciou_stage_grad.  CiouStageSrc derives them where they are needed from the raw row;
+// CiouNormSrc reads rows in which they were laid down before (the device kernel does that while it stages its tile, one
+// division per value instead of one per use).  Same expressions, same bits.
+LSN_HD float ciou_stage_p(float raw, float stride, float norm) { return raw * stride / norm; }
+LSN_HD float ciou_stage_d(float gt, float anchor, int has_object, float norm) { return has_object ? (gt - anchor) / norm : 0.f; }
+LSN_HD float ciou_stage_grad(float g, float stride, float norm) { return g * stride / norm; }
+// completed target of component c from the signed normalised offset of its pair
+LSN_HD float ciou_tt_signed(float d, int c, float alpha)
+{
+    const float m = fabsf(d);
+    const bool active = ((c & 1) != 0) == (d >= 0.f);
+    return active ? m : alpha * m;
+}
+
+struct CiouStageSrc {
+    const float *raw, *gt_pts;   // 4 (nv + 1) values in stride units; nv + 1 landmarks (x, y) in pixels
+    float ax, ay, stride, norm, alpha;
+    int has_object;
+    LSN_HDM float p(int c) const { return ciou_stage_p(raw[c], stride, norm); }
+    LSN_HDM float tt(int c) const
+    {
+        const int k = c >> 2, is_x = (c >> 1) & 1;
+        return ciou_tt_signed(ciou_stage_d(gt_pts[2 * k + 1 - is_x], is_x ? ax : ay, has_object, norm), c, alpha);
+    }
+};
+
+struct CiouNormSrc {
+    const float *pn, *dn;        // ciou_stage_p of the 4 (nv + 1) components; ciou_stage_d of the nv + 1 landmarks' (x, y)
+    float alpha;
+    LSN_HDM float p(int c) const { return pn[c]; }
+    LSN_HDM float tt(int c) const { return ciou_tt_signed(dn[2 * (c >> 2) + 1 - ((c >> 1) & 1)], c, alpha); }
+};
+
+// returns the unweighted loss; grad (M floats, may be NULL) receives d loss / d p.  Every s.p(c) is read before grad[c] is
+// written and the pairs of the box extremes are decided before the first write, so grad may be the memory s.p reads.
+template <class Src>
+LSN_HD float ciou_polygon_row_of(const Src &s, const float *anchor, const float *gt, int nv, int sub, float eps, float *grad)
 {
     const int M = 4 * (nv + 1);
     float smin[LSN_CIOU_MAXSUB], smax[LSN_CIOU_MAXSUB];
-    for (int s = 0; s < sub; ++s) smin[s] = smax[s] = 0.f;
-    for (int k = 0; k <= nv; ++k) {
-        const int s = k % sub;
+    for (int i = 0; i < sub; ++i) smin[i] = smax[i] = 0.f;
+    for (int k = 0, i = 0; k <= nv; ++k, i = (i + 1 == sub ? 0 : i + 1)) {   // i = k % sub
         for (int q = 0; q < 4; ++q) {
             const int c = 4 * k + q;
-            const float tt = ciou_tt(t, active, c, alpha);
-            smin[s] += fminf(p[c], tt);
-            smax[s] += fmaxf(p[c], tt);
+            const float p = s.p(c), tt = s.tt(c);
+            smin[i] += fminf(p, tt);
+            smax[i] += fmaxf(p, tt);
         }
     }
     float ov = 0.f;
-    for (int s = 0; s < sub; ++s) ov += smin[s] / smax[s];
+    for (int i = 0; i < sub; ++i) ov += smin[i] / smax[i];
     ov /= (float)sub;
     // bounding box of the nv vectors (the centre landmark is excluded); first extreme wins a tie
     int kx0 = 0, kx1 = 0, ky0 = 0, ky1 = 0;
     float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;
     for (int k = 0; k < nv; ++k) {
-        const float y = ciou_signed(p[4 * k], p[4 * k + 1]) + anchor[1], x = ciou_signed(p[4 * k + 2], p[4 * k + 3]) + anchor[0];
+        const float y = ciou_signed(s.p(4 * k), s.p(4 * k + 1)) + anchor[1], x = ciou_signed(s.p(4 * k + 2), s.p(4 * k + 3)) + anchor[0];
         if (k == 0 || x < bx0) bx0 = x, kx0 = k;
         if (k == 0 || x > bx1) bx1 = x, kx1 = k;
         if (k == 0 || y < by0) by0 = y, ky0 = k;
@@ -190,42 +242,110 @@ LSN_HD float cross_iou_polygon_row(const float *p, const float *t, const unsigne
     const float g_bx1 = dL_drho2 * (-dxs / 2) + dL_dc2 * 2.f * ew * cw * mx1 + dL_dv * dv_dw1;
     const float g_by0 = dL_drho2 * (-dys / 2) + dL_dc2 * 2.f * eh * ch * (-my0) + dL_dv * dv_dh1 * (-1.f);
     const float g_by1 = dL_drho2 * (-dys / 2) + dL_dc2 * 2.f * eh * ch * my1 + dL_dv * dv_dh1;
-    for (int c = 0; c < M; ++c) {
-        const int s = (c >> 2) % sub;
-        const float tt = ciou_tt(t, active, c, alpha);
-        grad[c] = dL_dov / (float)sub * (ciou_dmin(p[c], tt) / smax[s] - smin[s] / (smax[s] * smax[s]) * ciou_dmax(p[c], tt));
-    }
     // box coordinates -> the selected half of the pair of their extreme landmark
     const int pair_of[4] = {4 * kx0 + 2, 4 * ky0, 4 * kx1 + 2, 4 * ky1};
     const float g_box[4] = {g_bx0, g_by0, g_bx1, g_by1};
+    bool pos_half[4];
+    for (int q = 0; q < 4; ++q) pos_half[q] = s.p(pair_of[q] + 1) > s.p(pair_of[q]);
+    for (int k = 0, i = 0; k <= nv; ++k, i = (i + 1 == sub ? 0 : i + 1)) {
+        for (int q = 0; q < 4; ++q) {
+            const int c = 4 * k + q;
+            const float p = s.p(c), tt = s.tt(c);
+            grad[c] = dL_dov / (float)sub * (ciou_dmin(p, tt) / smax[i] - smin[i] / (smax[i] * smax[i]) * ciou_dmax(p, tt));
+        }
+    }
     for (int q = 0; q < 4; ++q) {
         const int c = pair_of[q];
-        if (p[c + 1] > p[c]) grad[c + 1] += g_box[q]; else grad[c] -= g_box[q];
+        if (pos_half[q]) grad[c + 1] += g_box[q]; else grad[c] -= g_box[q];
     }
     return loss;
 }
 
-// vs: nv visibility values (> 0 = counted)
-LSN_HD float cross_iou_keypoint_row(const float *p, const float *t, const unsigned char *active, const float *vs, int nv,
-                                    float alpha, float eps, float *grad)
+// vs: nv visibility values (> 0 = counted).  Both halves of a pair are read before either gradient is written: grad may be
+// the memory s.p reads.
+template <class Src>
+LSN_HD float ciou_keypoint_row_of(const Src &s, const float *vs, int nv, float eps, float *grad)
 {
     const int NP = 2 * (nv + 1);   // (neg, pos) pairs
     float sum = 0.f;
     for (int j = 0; j < NP; ++j) {
         const int c = 2 * j, k = j >> 1;
         const float vis = (k < nv) ? (vs[k] > 0.f ? 1.f : 0.f) : 1.f;
-        const float t0 = ciou_tt(t, active, c, alpha), t1 = ciou_tt(t, active, c + 1, alpha);
-        const float m0 = fmaxf(p[c], t0), m1 = fmaxf(p[c + 1], t1);
-        const float smn = fminf(p[c], t0) + fminf(p[c + 1], t1);
+        const float p0 = s.p(c), p1 = s.p(c + 1);
+        const float t0 = s.tt(c), t1 = s.tt(c + 1);
+        const float m0 = fmaxf(p0, t0), m1 = fmaxf(p1, t1);
+        const float smn = fminf(p0, t0) + fminf(p1, t1);
         const float smx = fmaxf(m0, eps) + fmaxf(m1, eps);
         sum += vis * smn / smx;
         if (grad) {
             // clamp(min = eps) passes the gradient where the value is >= eps
-            const float d0 = (m0 >= eps ? 1.f : 0.f) * ciou_dmax(p[c], t0), d1 = (m1 >= eps ? 1.f : 0.f) * ciou_dmax(p[c + 1], t1);
+            const float d0 = (m0 >= eps ? 1.f : 0.f) * ciou_dmax(p0, t0), d1 = (m1 >= eps ? 1.f : 0.f) * ciou_dmax(p1, t1);
             const float sc = -vis / (float)NP;
-            grad[c] = sc * (ciou_dmin(p[c], t0) / smx - smn / (smx * smx) * d0);
-            grad[c + 1] = sc * (ciou_dmin(p[c + 1], t1) / smx - smn / (smx * smx) * d1);
+            grad[c] = sc * (ciou_dmin(p0, t0) / smx - smn / (smx * smx) * d0);
+            grad[c + 1] = sc * (ciou_dmin(p1, t1) / smx - smn / (smx * smx) * d1);
         }
     }
     return 1.f - sum / (float)NP;
+}
+
+LSN_HD float cross_iou_polygon_row(const float *p, const float *t, const unsigned char *active, const float *anchor,
+                                   const float *gt, int nv, int sub, float alpha, float eps, float *grad)
+{
+    const CiouPlainSrc s = {p, t, active, alpha};
+    return ciou_polygon_row_of(s, anchor, gt, nv, sub, eps, grad);
+}
+
+LSN_HD float cross_iou_keypoint_row(const float *p, const float *t, const unsigned char *active, const float *vs, int nv,
+                                    float alpha, float eps, float *grad)
+{
+    const CiouPlainSrc s = {p, t, active, alpha};
+    return ciou_keypoint_row_of(s, vs, nv, eps, grad);
+}
+
+// ---- the whole regression stage of one point of the segm / pose tasks, as LSHead.loss_levels composes it -----------------
+// pred_raw: 4 (nv + 1) values in stride units; gt_pts: 2 (nv + 1) values, the nv landmarks and the centre as (x, y) in pixels;
+// anchor3 = (x, y, stride); gt_box: the ground-truth box in pixels.  p = raw * stride / norm, norm = base_scale * stride;
+// target, anchor and box are divided by norm; rows without an object have zero magnitudes.  grad (may be NULL, may be
+// pred_raw itself) receives d loss / d pred_raw.
+LSN_HD float cross_iou_polygon_stage_row(const float *pred_raw, const float *gt_pts, const float *anchor3, const float *gt_box,
+                                         int has_object, float base_scale, int nv, int sub, float alpha, float eps, float *grad)
+{
+    const float stride = anchor3[2], norm = base_scale * stride;
+    const CiouStageSrc s = {pred_raw, gt_pts, anchor3[0], anchor3[1], stride, norm, alpha, has_object};
+    const float an[2] = {anchor3[0] / norm, anchor3[1] / norm};
+    const float gb[4] = {gt_box[0] / norm, gt_box[1] / norm, gt_box[2] / norm, gt_box[3] / norm};
+    const float loss = ciou_polygon_row_of(s, an, gb, nv, sub, eps, grad);
+    if (grad)
+        for (int c = 0; c < 4 * (nv + 1); ++c) grad[c] = ciou_stage_grad(grad[c], stride, norm);
+    return loss;
+}
+
+LSN_HD float cross_iou_keypoint_stage_row(const float *pred_raw, const float *gt_pts, const float *anchor3, const float *vs,
+                                          int has_object, float base_scale, int nv, float alpha, float eps, float *grad)
+{
+    const float stride = anchor3[2], norm = base_scale * stride;
+    const CiouStageSrc s = {pred_raw, gt_pts, anchor3[0], anchor3[1], stride, norm, alpha, has_object};
+    const float loss = ciou_keypoint_row_of(s, vs, nv, eps, grad);
+    if (grad)
+        for (int c = 0; c < 4 * (nv + 1); ++c) grad[c] = ciou_stage_grad(grad[c], stride, norm);
+    return loss;
+}
+
+// The same rows on values laid down before: pn[c] = ciou_stage_p(raw[c]), dn[j] = ciou_stage_d(gt_pts[j]).  grad (may be NULL,
+// may be pn itself) receives d loss / d pn: the caller takes it through ciou_stage_grad.
+LSN_HD float cross_iou_polygon_stage_row_prepared(const float *pn, const float *dn, const float *anchor3, const float *gt_box,
+                                                  float base_scale, int nv, int sub, float alpha, float eps, float *grad)
+{
+    const float norm = base_scale * anchor3[2];
+    const CiouNormSrc s = {pn, dn, alpha};
+    const float an[2] = {anchor3[0] / norm, anchor3[1] / norm};
+    const float gb[4] = {gt_box[0] / norm, gt_box[1] / norm, gt_box[2] / norm, gt_box[3] / norm};
+    return ciou_polygon_row_of(s, an, gb, nv, sub, eps, grad);
+}
+
+LSN_HD float cross_iou_keypoint_stage_row_prepared(const float *pn, const float *dn, const float *vs, int nv, float alpha,
+                                                   float eps, float *grad)
+{
+    const CiouNormSrc s = {pn, dn, alpha};
+    return ciou_keypoint_row_of(s, vs, nv, eps, grad);
 }

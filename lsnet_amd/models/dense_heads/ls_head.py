@@ -679,6 +679,18 @@ class LSHead(nn.Module):
                         loss_fn.eps)
                     losses[f'{b}_{stage}'] = per_level_terms(rows, n)
                     continue
+                kind = getattr(loss_fn, 'loss_type', None)
+                if (b != 'bbox' and kind in ('polygon', 'keypoint') and fused_ciou.enabled() and fused_ciou.stage_enabled()
+                        and pred.is_cuda and pred.dtype == torch.float32
+                        and fused_ciou.stage_usable(kind, pred.reshape(-1, width), gt_pts, anchor, bbox_gt, kw.get('vs'), bw[:, 0],
+                                                    loss_fn.stride)):
+                    # (default; LSNET_CIOU_STAGE=0 switches it off) the same for the segm / pose stages: one launch each way
+                    # instead of the statements below and the fused rows behind loss_fn
+                    rows = loss_fn.loss_weight * fused_ciou.cross_iou_stage_rows(
+                        kind, pred.reshape(-1, width), gt_pts, anchor, bbox_gt, kw.get('vs'), bw[:, 0], self.point_base_scale,
+                        loss_fn.alpha, loss_fn.eps, loss_fn.stride)
+                    losses[f'{b}_{stage}'] = per_level_terms(rows, n)
+                    continue
                 pred = pred.reshape(-1, width) * stride
                 gt_reg, active = self._gt_reg(gt_pts, anchor, weights)
                 rows = loss_fn(pred / norm, gt_reg / norm, weights, reduction_override='none',
