@@ -40,25 +40,19 @@ class _BnActFn(torch.autograd.Function):
         need_p = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         dx = torch.empty_like(x, memory_format=_CL) if need_x else None
         dres = torch.empty_like(x, memory_format=_CL) if need_res else None
-        sg = grad_sink.sink(gamma) if ctx.needs_input_grad[2] else None
-        sb = grad_sink.sink(ctx.beta_ref) if ctx.needs_input_grad[3] else None
-        acc = 1 if (sg is not None and sb is not None) else 0
-        if acc:
-            dg, db = sg, sb
-        else:
+        c = grad_sink.claim([(gamma, ctx.needs_input_grad[2]), (ctx.beta_ref, ctx.needs_input_grad[3])])
+        if c.accumulate:
+            dg, db = c.sinks
+        else:       # (the one parameter pass writes both or neither)
             dg = torch.empty_like(gamma) if need_p else None
             db = torch.empty_like(gamma) if need_p else None
         lib = _lib.load()
         ws = torch.empty(lib.lsn_bn_eval_act_workspace_bytes(B * H * W, C), device=x.device, dtype=torch.uint8) \
             if need_p else None
         _lib.check(lib.lsn_bn_eval_act_backward(ptr(dy), ptr(y), ptr(x), ptr(mean), ptr(var), ptr(gamma), eps, 1 if relu else 0,
-                                                ptr(dx), ptr(dres), ptr(dg), ptr(db), ptr(ws), B * H * W, C, acc, stream()))
-        if acc:
-            grad_sink.done(gamma)
-            grad_sink.done(ctx.beta_ref)
-            dg = db = None
-        return dx, dres, dg if ctx.needs_input_grad[2] else None, db if ctx.needs_input_grad[3] else None, \
-            None, None, None, None
+                                                ptr(dx), ptr(dres), ptr(dg), ptr(db), ptr(ws), B * H * W, C, c.accumulate,
+                                                stream()))
+        return (dx, dres, *c.results((dg, db)), None, None, None, None)
 
 
 def _hip_ok(bn, x, residual):

@@ -88,25 +88,12 @@ def _forward_prepared(x, img, bias, w_shape, stride, pad, dil, relu, residual=No
 
 def _param_grad_buffers(w, bias, want_w, want_b):
     """Where a weight / bias gradient kernel writes: the parameters' gradient sinks (ops/grad_sink.py; accumulate = 1)
-    when BOTH wanted gradients have one, fresh tensors otherwise.  Returns (grad_w buffer, grad_b buffer or None, acc)."""
-    sw = grad_sink.sink(w) if want_w else None
-    sb = grad_sink.sink(bias) if (want_b and bias is not None) else None
-    if want_w and sw is not None and (not want_b or sb is not None) and sw.is_contiguous(memory_format=_CL) == \
-            w.is_contiguous(memory_format=_CL) and sw.stride() == w.stride():
-        return sw, sb, 1
-    gw = torch.empty_like(w)
-    gb = torch.empty(w.shape[0], device=w.device, dtype=torch.float32) if want_b else None
-    return gw, gb, 0
-
-
-def _param_grad_results(w, bias, gw, gb, acc, want_w):
-    """What the Function returns to autograd for (weight, bias) after the kernel ran."""
-    if acc:
-        grad_sink.done(w)
-        if gb is not None:
-            grad_sink.done(bias)
-        return None, None
-    return (gw if want_w else None), gb
+    when BOTH wanted gradients have one, fresh tensors otherwise (a grad_w scratch even when only the bias is wanted).
+    Returns (the claim, grad_w buffer, grad_b buffer or None)."""
+    c = grad_sink.claim([(w, want_w), (bias, want_b)], optional=(1,))
+    if c.accumulate:
+        return (c, *c.sinks)
+    return c, torch.empty_like(w), (torch.empty(w.shape[0], device=w.device, dtype=torch.float32) if want_b else None)
 
 
 # ---- kernel-level primitives (one C call each; the autograd Functions below and ops/resblock.py compose them) ----------
@@ -174,29 +161,18 @@ def wgrad_bn(x, g, w, bn, stride, pad, dil, need=(True, True, True)):
     B, C, H, W = x.shape
     Co, _, kh, kw = w.shape
     gamma, beta = bn.weight, bn.bias
-    sw, sg, sb = grad_sink.sink(w), grad_sink.sink(gamma), grad_sink.sink(beta)
-    acc = 1 if (all(need) and sw is not None and sg is not None and sb is not None and sw.stride() == w.stride()) else 0
-    if acc:
-        gw, dg, db = sw, sg, sb
-    else:
-        gw, dg, db = torch.empty_like(w), torch.empty_like(gamma), torch.empty_like(beta)
+    c = grad_sink.claim(list(zip((w, gamma, beta), need)))
+    gw, dg, db = c.sinks if c.accumulate else (torch.empty_like(w), torch.empty_like(gamma), torch.empty_like(beta))
     _lib.check(_lib.load().lsn_conv2d_backward_weight_bn(
         ptr(x), ptr(g), ptr(w), ptr(gamma), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(gw),
-        ptr(dg), ptr(db), B, H, W, C, Co, kh, kw, stride, pad, dil, acc, stream()))
-    if acc:
-        grad_sink.done(w)
-        grad_sink.done(gamma)
-        grad_sink.done(beta)
-        return None, None, None
-    return (gw if need[0] else None), (dg if need[1] else None), (db if need[2] else None)
+        ptr(dg), ptr(db), B, H, W, C, Co, kh, kw, stride, pad, dil, c.accumulate, stream()))
+    return c.results((gw, dg, db))
 
 
 def wgrad_bn_deferrable(w, bn):
     """Can this layer's parameter gradients be produced LATER, by a launch shared with other layers (wgrad_bn_jobs)?  Only
     into gradient sinks: autograd wants a returned gradient now."""
-    sw = grad_sink.sink(w)
-    return sw is not None and grad_sink.sink(bn.weight) is not None and grad_sink.sink(bn.bias) is not None \
-        and sw.stride() == w.stride() and w.is_cuda
+    return bool(grad_sink.claim([(w, True), (bn.weight, True), (bn.bias, True)]).accumulate and w.is_cuda)
 
 
 def wgrad_bn_jobs(jobs, stride, pad, dil):
@@ -206,20 +182,19 @@ def wgrad_bn_jobs(jobs, stride, pad, dil):
     B, C, H, W = x0.shape
     Co, _, kh, kw = w0.shape
     lib = _lib.load()
+    claims = [grad_sink.claim([(w, True), (bn.weight, True), (bn.bias, True)]) for _, _, w, bn in jobs]
+    assert all(c.accumulate for c in claims), 'wgrad_bn_jobs: a job whose parameters lost their sinks'
     for i in range(0, len(jobs), 8):
         part = jobs[i:i + 8]
         arr = (_lib.WgradBnJob * len(part))()
-        for q, (x, g, w, bn) in zip(arr, part):
+        for q, (x, g, w, bn), c in zip(arr, part, claims[i:i + 8]):
             assert x.shape == x0.shape and w.shape == w0.shape
             q.x, q.g, q.w = ptr(x), ptr(g), ptr(w)
             q.bn_gamma, q.bn_mean, q.bn_var, q.bn_eps = ptr(bn.weight), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps)
-            q.grad_w, q.grad_gamma, q.grad_beta = ptr(grad_sink.sink(w)), ptr(grad_sink.sink(bn.weight)), \
-                ptr(grad_sink.sink(bn.bias))
+            q.grad_w, q.grad_gamma, q.grad_beta = map(ptr, c.sinks)
         _lib.check(lib.lsn_conv2d_backward_weight_bn_jobs(len(part), arr, B, H, W, C, Co, kh, kw, stride, pad, dil, 1, stream()))
-    for _, _, w, bn in jobs:
-        grad_sink.done(w)
-        grad_sink.done(bn.weight)
-        grad_sink.done(bn.bias)
+    for c in claims:
+        c.results()
 
 
 def conv_fwd_bn(x, w, bn, stride, pad, dil, relu, residual=None):
@@ -259,10 +234,10 @@ class _ConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             # weight gradient and the bias gradient in one pass over grad_output
             want_b = has_bias and ctx.needs_input_grad[2]
-            gw, gb, acc = _param_grad_buffers(w, ctx.bias_ref if want_b else None, ctx.needs_input_grad[1], want_b)
+            c, gw, gb = _param_grad_buffers(w, ctx.bias_ref, ctx.needs_input_grad[1], want_b)
             _lib.check(lib.lsn_conv2d_backward_weight(ptr(x), ptr(go), ptr(gw), ptr(gb), B, H, W, C, Co, kh, kw, stride, pad,
-                                                      dil, acc, stream()))
-            gw, gb = _param_grad_results(w, ctx.bias_ref if want_b else None, gw, gb, acc, ctx.needs_input_grad[1])
+                                                      dil, c.accumulate, stream()))
+            gw, gb = c.results((gw, gb))
         return gx, gw, gb, None, None, None, None
 
 
@@ -372,9 +347,10 @@ def conv_multi_wgrad(xs, gos, w, bias, pad, dil, want_w=True, want_b=True):
         L = levels[i]
         L.x, L.grad_out, L.B, L.H, L.W = ptr(x), ptr(gos[i]), x.shape[0], x.shape[2], x.shape[3]
     want_b = want_b and bias is not None
-    gw, gb, acc = _param_grad_buffers(w, bias if want_b else None, want_w, want_b)
-    _lib.check(_lib.load().lsn_conv2d_backward_weight_multi(n, levels, ptr(gw), ptr(gb), C, Co, kh, kw, 1, pad, dil, acc, stream()))
-    return _param_grad_results(w, bias if want_b else None, gw, gb, acc, want_w)
+    c, gw, gb = _param_grad_buffers(w, bias, want_w, want_b)
+    _lib.check(_lib.load().lsn_conv2d_backward_weight_multi(n, levels, ptr(gw), ptr(gb), C, Co, kh, kw, 1, pad, dil, c.accumulate,
+                                                            stream()))
+    return c.results((gw, gb))
 
 
 class _ConvMultiFn(torch.autograd.Function):

@@ -37,6 +37,18 @@ def _same_int(v, what):
     return int(v[0])
 
 
+def _backend_backward(ctx, inputs, offsets, masks, weight, gos, need):
+    """ctx.backend.dcn_backward with (weight, bias) claimed: the parameter gradients go straight into their sinks (the all-
+    reduce buckets) when both wanted ones have one and the backend takes sinks for these layouts (`dcn_sinks_ok`).
+    -> (grad_inputs, grad_offsets, grad_masks, grad_weight, grad_bias), the last two as autograd gets them."""
+    sinks_ok = getattr(ctx.backend, 'dcn_sinks_ok', None)
+    c = grad_sink.claim([(weight, need['weight']), (ctx.bias_ref, need['bias'])], optional=(1,),
+                        allowed=sinks_ok is not None and sinks_ok(inputs, weight))
+    kw = dict(sinks=c.sinks) if c.accumulate else {}
+    gxs, goffs, gmsks, gw, gb = ctx.backend.dcn_backward(inputs, offsets, masks, weight, gos, ctx.cfg, need, **kw)
+    return (gxs, goffs, gmsks, *c.results((gw, gb)))
+
+
 class _DCNFunction(Function):
     """forward(weight, bias, cfg, n, x_0..x_{n-1}, off_0..off_{n-1}, mask_0..mask_{n-1})"""
 
@@ -101,28 +113,14 @@ class _DCNFunction(Function):
                 x, off = inputs[i], offsets[i]
                 g = x.new_zeros((x.shape[0], weight.shape[0], off.shape[2], off.shape[3]))
             gos.append(g)
-        # parameter gradients straight into their sinks (the all-reduce buckets) when both have one
-        sw = grad_sink.sink(weight) if need['weight'] else None
-        sb = grad_sink.sink(ctx.bias_ref) if need['bias'] else None
-        sunk = sw is not None and (not need['bias'] or sb is not None) and sw.stride() == weight.stride() \
-            and getattr(ctx.backend, 'supports_grad_sinks', False)
-        if sunk:
-            need['sinks'] = (sw, sb)
-        gxs, goffs, gmsks, gw, gb = ctx.backend.dcn_backward(list(inputs), list(offsets), masks, weight, gos,
-                                                            cfg, need)
-        if sunk and need.get('sunk'):
-            grad_sink.done(weight)
-            if sb is not None:
-                grad_sink.done(ctx.bias_ref)
-            gw = gb = None
+        gxs, goffs, gmsks, gw, gb = _backend_backward(ctx, list(inputs), list(offsets), masks, weight, gos, need)
         gxs = [g if need['input'][i] else None for i, g in enumerate(gxs)]
         goffs = [g if need['offset'][i] else None for i, g in enumerate(goffs)]
         gmsks = [g if (need['mask'][i] and not ctx.mask_none[i]) else None for i, g in enumerate(gmsks)]
         if gw is not None and gw.stride() != weight.stride():
             gw = gw.contiguous(memory_format=torch.channels_last if weight.is_contiguous(
                 memory_format=torch.channels_last) and not weight.is_contiguous() else torch.contiguous_format)
-        return (gw if need['weight'] else None, gb if (need['bias'] and gb is not None) else None, None, None,
-                *gxs, *goffs, *gmsks)
+        return (gw, gb, None, None, *gxs, *goffs, *gmsks)
 
 
 class _DCNPackFn(Function):
@@ -161,26 +159,14 @@ class _DCNPackFn(Function):
                     offset=[need_off] * n, mask=[False] * n)
         gos = [g if g is not None else x.new_zeros((x.shape[0], weight.shape[0], o.shape[2], o.shape[3]))
                for g, x, o in zip(grad_outs, xs, offs)]
-        sw = grad_sink.sink(weight) if need['weight'] else None
-        sb = grad_sink.sink(ctx.bias_ref) if need['bias'] else None
-        sunk = sw is not None and (not need['bias'] or sb is not None) and sw.stride() == weight.stride() \
-            and getattr(ctx.backend, 'supports_grad_sinks', False)
-        if sunk:
-            need['sinks'] = (sw, sb)
-        gxs, goffs, _, gw, gb = ctx.backend.dcn_backward(list(xs), list(offs), [None] * n, weight, gos, cfg, need)
-        if sunk and need.get('sunk'):
-            grad_sink.done(weight)
-            if sb is not None:
-                grad_sink.done(ctx.bias_ref)
-            gw = gb = None
+        gxs, goffs, _, gw, gb = _backend_backward(ctx, list(xs), list(offs), [None] * n, weight, gos, need)
         pad, dil = cfg['pad'], cfg['dil']
         if any(need_x):   # conv_offset's data gradient lands ON the deformable op's grad_input
             gxs = _conv.conv_multi_dgrad(goffs, w_off, xs, pad, dil, accumulate_into=gxs)
         gwo = gbo = None
         if nig[2] or nig[3]:
             gwo, gbo = _conv.conv_multi_wgrad(xs, goffs, w_off, ctx.b_off_ref, pad, dil, nig[2], nig[3])
-        return (gw if need['weight'] else None, gb if (need['bias'] and gb is not None) else None, gwo, gbo, None, None,
-                *[g if nx else None for g, nx in zip(gxs, need_x)])
+        return (gw, gb, gwo, gbo, None, None, *[g if nx else None for g, nx in zip(gxs, need_x)])
 
 
 class _OffsetChainFn(Function):

@@ -17,6 +17,20 @@ from .backend import get_backend
 _CL = torch.channels_last
 
 
+def _backward(ctx, dys):
+    """The backward pass of both Functions below; dys: one gradient per level, or the one gradient of a cat_px output."""
+    gamma, beta, mean_rstd, *xs = ctx.saved_tensors
+    groups, relu = ctx.cfg
+    want_g, want_b = ctx.needs_input_grad[:2]
+    be = get_backend(xs[0])
+    c = grad_sink.claim([(gamma, want_g), (beta, want_b)], allowed=getattr(be, 'supports_grad_sinks', False))
+    if c.accumulate:
+        dxs, dg, db = be.group_norm_backward(xs, dys, gamma, beta, groups, relu, mean_rstd, True, sinks=c.sinks)
+    else:
+        dxs, dg, db = be.group_norm_backward(xs, dys, gamma, beta, groups, relu, mean_rstd, want_g or want_b)
+    return (*c.results((dg, db)), None, None, None, *dxs)
+
+
 class _GroupNormCatFn(torch.autograd.Function):
     """GroupNorm (+ ReLU) of the levels of a shared module whose outputs are wanted as LSHead._cat_px would lay them out: one
     (B, C, N_all, 1) tensor, the pixel rows of all levels back to back.  The kernels write the levels where they belong and
@@ -35,20 +49,7 @@ class _GroupNormCatFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        gamma, beta, mean_rstd, *xs = ctx.saved_tensors
-        groups, relu = ctx.cfg
-        need_p = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        be = get_backend(xs[0])
-        sg = grad_sink.sink(gamma) if ctx.needs_input_grad[0] else None
-        sb = grad_sink.sink(beta) if ctx.needs_input_grad[1] else None
-        sinks = (sg, sb) if (sg is not None and sb is not None and getattr(be, 'supports_grad_sinks', False)) else None
-        if sinks:
-            dxs, _, _ = be.group_norm_backward(xs, dy, gamma, beta, groups, relu, mean_rstd, True, sinks=sinks)
-            grad_sink.done(gamma)
-            grad_sink.done(beta)
-            return (None, None, None, None, None, *dxs)
-        dxs, dg, db = be.group_norm_backward(xs, dy, gamma, beta, groups, relu, mean_rstd, need_p)
-        return (dg if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None, *dxs)
+        return _backward(ctx, dy)
 
 
 class _GroupNormFn(torch.autograd.Function):
@@ -64,22 +65,8 @@ class _GroupNormFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *dys):
-        gamma, beta, mean_rstd, *xs = ctx.saved_tensors
-        groups, relu = ctx.cfg
-        dys = [torch.zeros_like(x) if d is None else d for d, x in zip(dys, xs)]
-        need_p = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        be = get_backend(xs[0])
-        sg = grad_sink.sink(gamma) if ctx.needs_input_grad[0] else None
-        sb = grad_sink.sink(beta) if ctx.needs_input_grad[1] else None
-        sinks = (sg, sb) if (sg is not None and sb is not None and getattr(be, 'supports_grad_sinks', False)) else None
-        if sinks:
-            dxs, _, _ = be.group_norm_backward(xs, dys, gamma, beta, groups, relu, mean_rstd, True, sinks=sinks)
-            grad_sink.done(gamma)
-            grad_sink.done(beta)
-            return (None, None, None, None, None, *dxs)
-        dxs, dg, db = be.group_norm_backward(xs, dys, gamma, beta, groups, relu, mean_rstd, need_p)
-        return (dg if ctx.needs_input_grad[0] else None, db if ctx.needs_input_grad[1] else None, None, None, None,
-                *dxs)
+        xs = ctx.saved_tensors[3:]
+        return _backward(ctx, [torch.zeros_like(x) if d is None else d for d, x in zip(dys, xs)])
 
 
 def _hip_ok(x, C, G):

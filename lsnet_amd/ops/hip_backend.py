@@ -271,8 +271,15 @@ class HipBackend:
             return wide if wide is not None else [torch.cat(outs[j:j + g], dim=1) for j in range(0, n, g)]
         return outs
 
-    def dcn_backward(self, inputs, offsets, masks, weight, grad_outs, cfg, need):
-        """need: dict(input=[bool]*n, offset=[bool]*n, mask=[bool]*n, weight=bool, bias=bool).
+    @staticmethod
+    def dcn_sinks_ok(inputs, weight):
+        """May dcn_backward be handed `sinks` for these tensors?  Only where the kernels write the gradient of `weight` itself:
+        channels-last inputs and a weight `_prep` passes on as it is (not a re-laid temporary)."""
+        return all(_is_nhwc(x) for x in inputs) and weight.is_contiguous(memory_format=_CL)
+
+    def dcn_backward(self, inputs, offsets, masks, weight, grad_outs, cfg, need, sinks=None):
+        """need: dict(input=[bool]*n, offset=[bool]*n, mask=[bool]*n, weight=bool, bias=bool).  sinks: (grad_weight, grad_bias
+        or None) buffers to ADD the parameter gradients to (ops/grad_sink.py), for calls that pass `dcn_sinks_ok`.
         Returns (grad_inputs, grad_offsets, grad_masks, grad_weight, grad_bias)."""
         nhwc, xs, offs, msks, w = self._prep(inputs, offsets, masks, weight)
         n = len(xs)
@@ -299,11 +306,10 @@ class HipBackend:
             gmsks.append(torch.empty_like(msks[i]) if (want_om and msks[i] is not None) else None)
             gxs.append(gx_ret)
             bufs.append(gx)
-        sinks = need.get('sinks') if (nhwc and w is weight) else None
-        if sinks is not None:     # accumulate into the caller's gradient arena (ops/grad_sink.py)
+        if sinks is not None:     # accumulate into the caller's gradient arena
+            assert nhwc and w is weight, 'dcn_backward: sinks for a call that dcn_sinks_ok declines'
             gw, gb = sinks
             acc = 1
-            need['sunk'] = True
         else:
             gw = torch.empty_like(w) if (need['weight'] or need['bias']) else None
             gb = torch.empty(w.shape[0], device=w.device, dtype=torch.float32) if need['bias'] else None

@@ -420,6 +420,37 @@ def test_parameter_gradients_onto_non_zero_sinks(case, tol):
             _line(f'sunk {state} {case.op} {case.name}', errs)
 
 
+@pytest.mark.parametrize('variant', ['nchw_inputs', 'contiguous_weight'])
+def test_dcn_sinks_declined_for_the_layout_take_the_classic_path(variant):
+    """dcn_multi on 'xn' with sinks for w and b where the device backend declines them: inputs in contiguous (NCHW) memory, and
+    channels-last inputs under a contiguous (not channels-last) weight parameter, which the backend re-lays into a temporary.
+    Both gradients go back to autograd, whose AccumulateGrad adds them into the registered views: the leaf hooks see w and b,
+    nobody is told `done`, p.grad is still the view, base + gradient within DCN_TOL, canaries bit-identical."""
+    from lsnet_amd.ops import grad_sink
+    case = br.DCN['xn']
+    nhwc = variant == 'contiguous_weight'
+    with _math('bf16x6'):
+        ref = br.reference(case)
+        leaves, t = _tensors(case, ref, br.leaf_names(case), nhwc)
+        if nhwc:
+            t['w'] = leaves['w'] = torch.nn.Parameter(leaves['w'].detach().contiguous())
+        assert t['x'].is_contiguous(memory_format=_CL) == nhwc and not t['w'].is_contiguous(memory_format=_CL)
+        params = collections.OrderedDict((n, leaves[n]) for n in ('w', 'b'))
+        views, before, index = br.arena(params, ref.grads, seed=case.seed)
+        done, returned = collections.Counter(), collections.Counter()
+        for n, p in params.items():
+            grad_sink.register(p, views[n], on_done=lambda p, n=n: done.update([n]))
+            p.grad = views[n]
+            p.register_hook(lambda g, n=n: returned.update([n] if g is not None else []))
+        br.backward(br.dcn_outputs(case, t), _upstream(case, ref, nhwc), {})
+        torch.cuda.synchronize()
+        assert returned == collections.Counter(w=1, b=1) and not done, (returned, done)
+        for n, p in params.items():
+            assert p.grad is views[n] and p.grad.data_ptr() == views[n].data_ptr(), n
+        errs = br.check_sunk(index['flat'], before, ref.grads, DCN_TOL, index)
+        _line(f'sunk declined {variant} {case.op} {case.name}', errs)
+
+
 @pytest.mark.parametrize('with_bias', [True, False])
 def test_grouped_conv_weight_gradient_accumulates_at_the_c_entry(with_bias):
     """lsn_grouped_conv2d_backward_weight(accumulate = 1), which _GroupConvFn never passes: onto non-zero grad_w / grad_bias, and

@@ -236,7 +236,7 @@ def test_fused_logits_form_behind_the_oracle(cpu_oracle_backend):
 
 @pytest.mark.parametrize('state', ['all_sunk', 'weight_only', 'bias_frozen'])
 def test_sinks_on_cpu_parameters_take_the_classic_path(state, cpu_oracle_backend):
-    """Sinks registered on CPU parameters: the oracle backend has no `supports_grad_sinks`, so _DCNFunction returns its
+    """Sinks registered on CPU parameters: the oracle backend has no `dcn_sinks_ok`, so _DCNFunction returns its
     gradients and AccumulateGrad ADDS them into the registered view; p.grad stays that view, nobody is told `done`."""
     from lsnet_amd.ops import grad_sink
     case = br.DCN['xn']
