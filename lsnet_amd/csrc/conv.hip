@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conv_kernels.h"
+#include "conv_route.h"
 #include "conv_wgrad_kernels.h"
 #include "lib_state.h"
 #include "prof.h"
@@ -60,72 +61,22 @@ int wgrad_part_buffer(size_t floats, float **p, hipStream_t st)
     return stream_scratch(floats, p, st);
 }
 
-// Work distribution of one launch (conv_kernels.h ConvArgs).  The chip holds 512 workgroups of these kernels at once, so
-// a launch of W tiles runs in ceil(W / 512) rounds and the last one is rarely full: 525 tiles (every convolution at the
-// 100 x 168 maps of two images) cost 226 us against 177 us for 512 (tools/ubench/tile_sweep), 132 or 33 tiles (stages 3 / 4)
-// leave most of the chip idle.  Rounds 3 / 4 answered with a reduction split over blockIdx.z plus a reduce launch, and a
-// second launch for the tail; both quantise again (the split rule produced 528 workgroups for six layer shapes of the
-// step).  Round 5: the last 512 + r tiles of a launch -- or all of them when there are fewer than 512 -- are divided
-// EVENLY BY CHUNKS over 512 workgroups, whole tiles before them stay one workgroup each.
-// Not for short reductions (< 16 chunks: the layer is bound by its output stream, and a partial tile costs what the tile
-// costs) and not when the last round is nearly full.
-static void sk_plan(int ntw, int Tall, int *n_dp, int *sk_n, int *sk_tiles)
-{
-    *n_dp = ntw, *sk_n = 0, *sk_tiles = 0;
-    constexpr int SLOTS = 512;
-    // (launches of two or more whole rounds lose more to the segment loop's longer prologue in EVERY workgroup than the
-    // last round can return: profiles/r5_sk_policy.txt, layer-1 rows)
-    if (Tall < 8 || ntw >= 2 * SLOTS) return;
-    const int r = ntw % SLOTS;
-    if (r == 0 || r > 448) return;
-    // Pieces per tile: at most four when the pieces are the whole launch (the tile's last arriver adds them on its own), up
-    // to sixteen for the few tiles behind a whole round (the chip is idle otherwise); never shorter than four chunks.
-    int per_tile = Tall / 4;
-    const int cap = ntw > SLOTS ? 16 : 4;
-    if (per_tile > cap) per_tile = cap;
-    const long long pieces = (long long)r * per_tile;
-    const int ns = pieces < SLOTS ? (int)pieces : SLOTS;
-    if (ns <= r) return;
-    *n_dp = ntw - r, *sk_n = ns, *sk_tiles = r;
-}
+static_assert(CR_MAXLV == CV_MAXLV && CR_SK_MAX_TILES == SK_MAX_TILES, "conv_route.h mirrors the library's constants");
+static_assert(cr_ncc(1) == cv_ncc(1) && cr_ncc(32) == cv_ncc(32) && cr_ncc(33) == cv_ncc(33), "conv_route.h counts chunks as cv_ncc");
 
-// Fewer than 512 tiles and more than four pieces per tile (stage 4, FPN P5: 33 pixel tiles under 64 .. 144 chunks): the tile's
-// last arriver would add eight partial tiles on its own while the chip idles -- these keep round 3's blockIdx.z split with its
-// chip-wide reduce launch, rounded DOWN to one round of workgroups (round 3 / 4 rounded to nearest: 528 on 512 slots for six
-// layer shapes of the step).
-static int z_split(int ntw, int Tall)
-{
-    if (ntw >= 128 || Tall < 16) return 1;
-    int ks = 512 / ntw;
-    if (ks > Tall / 8) ks = Tall / 8;
-    if (ks > 16) ks = 16;
-    return ks < 1 ? 1 : ks;
-}
-
-// One launch over the pixel tiles [tile_base, tile_base + ntiles) of the (tiled) levels, `ks` chunk splits (the round-3
-// form with its reduce launch: only where stream-K does not apply).
+// One launch of a routed tile (conv_route.h): the scratch the route asks for, the LDS attribute, the launch, and the reduce
+// launch behind blockIdx.z splits.
 template <int TM, int TN, int WM, int WN, int NP, bool UNAL, bool FINE, bool TRANS>
-static int launch_conv_range(ConvArgs &a, int ks, int tile_base, int ntiles, hipStream_t st)
+static int launch_conv_tile(ConvArgs &a, hipStream_t st)
 {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const size_t lds = (size_t)2 * SplitCfg<NP>::NPL * BM * 64;
-    a.colblocks = (a.Co + BN - 1) / BN;
-    const int ntw = ntiles * a.colblocks;
-    a.n_dp = ntw, a.sk_n = 0, a.sk_tiles = 0, a.sk_part = nullptr, a.sk_cnt = nullptr;
-    if (ks == 1 && !TRANS) {
-        sk_plan(ntw, a.kh * a.kw * cv_ncc(a.C), &a.n_dp, &a.sk_n, &a.sk_tiles);
-        // (the kernel's unit arithmetic is 32-bit: (U + 1) * sk_n must stay below 2^31)
-        if (a.sk_tiles > SK_MAX_TILES || ((long long)a.sk_tiles * a.kh * a.kw * cv_ncc(a.C) + 1) * a.sk_n >= ((long long)1 << 31))
-            a.n_dp = ntw, a.sk_n = 0, a.sk_tiles = 0;
-        if (a.sk_n) {
-            if (int rc = stream_sk_scratch((size_t)2 * a.sk_n * BM * BN, &a.sk_part, &a.sk_cnt, st)) return rc;
-        }
-    }
-    a.ksplit = ks;
-    a.tile_base = tile_base;
-    const int pix0 = tile_base * BM;   // (ks > 1: one level)
-    const int rows = ks > 1 ? (a.lv[0].P - pix0 < ntiles * BM ? a.lv[0].P - pix0 : ntiles * BM) : 0;
-    a.part_pix0 = pix0, a.part_rows = rows;
+    const int ks = a.ksplit;
+    a.sk_part = nullptr, a.sk_cnt = nullptr;
+    if (a.sk_n)
+        if (int rc = stream_sk_scratch((size_t)2 * a.sk_n * BM * BN, &a.sk_part, &a.sk_cnt, st)) return rc;
+    const int rows = ks > 1 ? a.lv[0].P : 0;   // (ks > 1: one level)
+    a.part_pix0 = 0, a.part_rows = rows;
     const size_t n = (size_t)rows * a.Co;
     if (ks > 1)
         if (int rc = stream_scratch(n * ks, &a.part, st)) return rc;
@@ -143,81 +94,47 @@ static int launch_conv_range(ConvArgs &a, int ks, int tile_base, int ntiles, hip
     if (int rc = a.sk_n ? launch(std::true_type()) : launch(std::false_type())) return rc;
     if (ks > 1) {
         const int blocks = (int)((n / 4 + 255) / 256 < 1024 ? (n / 4 + 255) / 256 : 1024);
-        const size_t o = (size_t)pix0 * a.Co;
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a.part, a.lv[0].out + o, a.bias,
-                           a.lv[0].res ? a.lv[0].res + o : nullptr, a.lv[0].gate ? a.lv[0].gate + o : nullptr, (int)n, a.Co, ks,
-                           a.relu);
+        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a.part, a.lv[0].out, a.bias,
+                           a.lv[0].res, a.lv[0].gate, (int)n, a.Co, ks, a.relu);
     }
     LSN_HIP(hipGetLastError());
     return 0;
 }
 
-template <int TM, int TN, int WM, int WN, int NP, bool UNAL, bool FINE, bool TRANS = false>
-static int launch_conv_cfg(ConvArgs &a, int ks, hipStream_t st)
+enum ConvKind { CONV_FWD, CONV_BWD_DATA, CONV_ROWS };   // CONV_ROWS: conv_mm_rows, its row blocks at 32-bit byte offsets
+
+// The route (conv_route.h) of the launch that `a` describes.
+static ConvRoute conv_route_of(const ConvArgs &a, ConvKind kind, bool rows32 = false)
 {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    int tiles = 0;
-    for (int i = 0; i < a.nlv; ++i) {
-        a.lv[i].tile0 = tiles;
-        tiles += (a.lv[i].P + BM - 1) / BM;
-    }
-    a.ntiles = tiles;
-    return launch_conv_range<TM, TN, WM, WN, NP, UNAL, FINE, TRANS>(a, ks, 0, tiles, st);
+    ConvRouteShape s = {};
+    s.n = a.nlv;
+    for (int i = 0; i < a.nlv; ++i) s.P[i] = a.lv[i].P;
+    s.C = a.C, s.xpitch = a.xpitch, s.Co = a.Co, s.taps = a.kh * a.kw;
+    s.ostep = a.ostep != 0, s.data_grad = kind == CONV_BWD_DATA, s.rows_gemm = kind == CONV_ROWS, s.rows32 = rows32;
+    return conv_route(s);
 }
 
+// Writes the route into `a` and runs the tile's kernel; the one place that refuses what the route refuses.
 // FINE: the fine MFMA / staging interleave (conv_kernels.h) -- adopted for the two wide tiles after the round-4 sweep; for
 // the two narrow ones (Co <= 64) it measured no difference (4216 / 3095 vs 4218 / 3105 us, profiles/r4_conv_tiles.txt)
-template <int TM, int TN, int WM, int WN, bool FINE>
-static int launch_conv(ConvArgs &a, int ks, hipStream_t st)
+static int conv_launch(ConvArgs &a, const ConvRoute &r, hipStream_t st)
 {
-    if constexpr (TN == 2 && WN == 2) {   // the unaligned-slab variant exists for the 64 x 128 tile
-        if (a.C % 4 != 0 || a.xpitch % 4 != 0)
-            return split_dispatch(conv_np(), [&](auto np) {
-                return launch_conv_cfg<TM, TN, WM, WN, decltype(np)::value, true, false>(a, ks, st);
-            });
-    }
-    if (a.C % 4 != 0 || a.xpitch % 4 != 0)
-        return fail(LSN_ERR_UNSUPPORTED, "conv2d: C %% 4 != 0 needs more than 64 output channels");
-    return split_dispatch(conv_np(), [&](auto np) {
-        return launch_conv_cfg<TM, TN, WM, WN, decltype(np)::value, false, FINE>(a, ks, st);
+    if (r.unsupported) return fail(LSN_ERR_UNSUPPORTED, "%s", r.unsupported);
+    for (int i = 0; i < a.nlv; ++i) a.lv[i].tile0 = r.tile0[i];
+    a.ntiles = r.tiles, a.tile_base = 0, a.colblocks = r.colblocks, a.ksplit = r.ks;
+    a.n_dp = r.sk.n_dp, a.sk_n = r.sk.sk_n, a.sk_tiles = r.sk.sk_tiles;
+    return split_dispatch(conv_np(), [&](auto np) -> int {
+        constexpr int NP = decltype(np)::value;
+        switch (r.tile) {
+        case CT_128x32: return launch_conv_tile<1, 1, 4, 1, NP, false, false, false>(a, st);
+        case CT_128x64: return launch_conv_tile<1, 2, 4, 1, NP, false, false, false>(a, st);
+        case CT_64x128: return launch_conv_tile<1, 2, 2, 2, NP, false, true, false>(a, st);
+        case CT_64x128_UNAL: return launch_conv_tile<1, 2, 2, 2, NP, true, false, false>(a, st);
+        case CT_64x256: return launch_conv_tile<2, 2, 1, 4, NP, false, true, false>(a, st);
+        case CT_64x256_ROWS: return launch_conv_tile<2, 2, 1, 4, NP, false, true, true>(a, st);
+        }
+        return fail(LSN_ERR_INVALID, "conv2d: no kernel for tile %d", (int)r.tile);
     });
-}
-
-// Tile choice (pixels x output channels per workgroup; two workgroups share a CU, so the chip holds 512 of them at
-// once).  Round-4 sweep over the step's layer shapes (tools/ubench/conv_step, profiles/r4_conv_tiles.txt):
-//   * 64 x 256 (a pixel slab is fetched and split ONCE for 256 output channels: half the split work per MFMA of the
-//     128-wide tiles) wins wherever Co is a multiple of 256 and the reduction is deep (3x3) or the launch fills a round;
-//   * 64 x 128 otherwise for Co > 64; 128 x 64 / 128 x 32 for the narrow outputs;
-//   * 128 x 128 lost on every row (fewer, longer workgroups) and the one-workgroup-per-CU fat register tiles
-//     (256 x 128, 128 x 256) lost by 30 %: both are gone.
-// When even the narrow tile leaves most of the chip idle (few pixels under a deep reduction: layer 4, FPN P5 .. P7) the
-// chunk range is split over blockIdx.z into partial tiles that a second small kernel adds up
-// (profiles/r3_conv_ksplit.txt; forcing other split counts lost on every row of the round-4 sweep).
-static int conv_forward(ConvArgs &a, hipStream_t st)
-{
-    auto blocks = [&](int bm, int bn) {
-        int t = 0;
-        for (int i = 0; i < a.nlv; ++i) t += (a.lv[i].P + bm - 1) / bm;
-        return t * ((a.Co + bn - 1) / bn);
-    };
-    int cfg;   // 2: 64 x 128, 3: 128 x 64, 4: 128 x 32, 5: 64 x 256
-    if (a.Co <= 32) cfg = 4;
-    else if (a.Co <= 64) cfg = 3;
-    else cfg = 2;
-    // (round 5, with stream-K filling the chip either way: 64 x 256 for EVERY Co % 256 == 0 lost 3 % over the step's shapes,
-    // forward 3944 -> 4078 us, data gradient 2871 -> 2959 us, tools/ubench/conv_step A/B -- the rule stands)
-    if (a.Co % 256 == 0 && a.C % 4 == 0 && a.xpitch % 4 == 0 && (a.kh * a.kw > 1 || blocks(64, 256) >= 512)) cfg = 5;
-    const int nb = cfg == 2 ? blocks(64, 128) : cfg == 3 ? blocks(128, 64) : cfg == 5 ? blocks(64, 256) : blocks(128, 32);
-    const int Tall = a.kh * a.kw * cv_ncc(a.C);
-    int ks = 1;
-    // round 5: stream-K pieces (sk_plan) wherever a tile gets at most four of them, blockIdx.z splits + a reduce launch below
-    if (a.nlv == 1 && !a.ostep) ks = z_split(nb, Tall);
-    switch (cfg) {
-    case 2: return launch_conv<1, 2, 2, 2, true>(a, ks, st);
-    case 3: return launch_conv<1, 2, 4, 1, false>(a, ks, st);
-    case 5: return launch_conv<2, 2, 1, 4, true>(a, ks, st);
-    default: return launch_conv<1, 1, 4, 1, false>(a, ks, st);
-    }
 }
 
 // dcn.hip: out_i[r][0 .. N) = x_i[r][0 .. Cr) . Wt for row blocks i (the backward-data GEMM of the deformable
@@ -240,12 +157,7 @@ int conv_mm_rows(int n, const float *const *x, float *const *out, const int *row
     a.xpitch = xpitch;
     bool rows32 = true;   // the TRANS epilogue stores through a buffer descriptor of each row block: 32-bit byte offsets
     for (int i = 0; i < n; ++i) rows32 = rows32 && (long long)rows[i] * N * 4 < (1ll << 31) - 256;
-    if (N % 256 == 0 && rows32) {   // the 64 x 256 tile with whole-line stores (conv_kernels.h TRANS); plain output, one split
-        return split_dispatch(conv_np(), [&](auto np) {
-            return launch_conv_cfg<2, 2, 1, 4, decltype(np)::value, false, true, true>(a, 1, st);
-        });
-    }
-    return conv_forward(a, st);
+    return conv_launch(a, conv_route_of(a, CONV_ROWS, rows32), st);
 }
 
 // optional folded BatchNorm of a prepare call (all NULL: a plain weight)
@@ -366,8 +278,6 @@ static int conv_forward_impl(int n, const lsn_conv_level *lv, const void *prepar
     LSN_CHECK(n >= 1 && n <= CV_MAXLV && lv && prepared, "conv2d: bad level list");
     LSN_CHECK(xpitch > 0, "conv2d: bad pixel pitch %d", xpitch);
     LaunchLog log(0, n, lv, C, xpitch, Co, kh, kw, stride, pad, dil, relu, st);
-    if ((C % 4 != 0 || xpitch % 4 != 0) && Co <= 64)
-        return fail(LSN_ERR_UNSUPPORTED, "conv2d: C %% 4 != 0 needs more than 64 output channels");
     ConvArgs a = {};
     a.nlv = n;
     for (int i = 0; i < n; ++i) {
@@ -392,7 +302,7 @@ static int conv_forward_impl(int n, const lsn_conv_level *lv, const void *prepar
     a.xpitch = xpitch;
     a.relu = relu;
     ConvProf prof(PROF_CONV_FWD, a, st);
-    return conv_forward(a, st);
+    return conv_launch(a, conv_route_of(a, CONV_FWD), st);
 }
 
 // Residue classes of the transposed convolution (backward-data of a stride-s convolution):
@@ -464,7 +374,6 @@ static int conv_backward_data_impl(int n, const lsn_conv_level *lv, const void *
 {
     LSN_CHECK(n >= 1 && n <= CV_MAXLV && lv && prepared, "conv2d backward: bad arguments");
     LaunchLog log(1, n, lv, C, C, Co, kh, kw, stride, pad, dil, 0, st);
-    if (Co % 4 != 0 && C <= 64) return fail(LSN_ERR_UNSUPPORTED, "conv2d backward-data: Co %% 4 != 0 needs C > 64");
     const int s = stride;
     int Ho[CV_MAXLV], Wo[CV_MAXLV];
     for (int i = 0; i < n; ++i) {
@@ -501,7 +410,7 @@ static int conv_backward_data_impl(int n, const lsn_conv_level *lv, const void *
         a.pad_h = c.pad_h, a.pad_w = c.pad_w, a.dil = c.dstep;
         if (s > 1) a.ostep = s, a.oy0 = c.py, a.ox0 = c.px, a.OH = H, a.OW = W;
         ConvProf prof(PROF_CONV_BWD_DATA, a, st);
-        if (int rc = conv_forward(a, st)) return rc;
+        if (int rc = conv_launch(a, conv_route_of(a, CONV_BWD_DATA), st)) return rc;
     }
     return 0;
 }

@@ -53,14 +53,14 @@ struct ConvArgs {
                   // pixels under a deep reduction (layer 4, FPN P5 .. P7) would otherwise leave most CUs idle; fp32
                   // atomics into the output were measured 5 - 10 x slower than the whole convolution.
     float *part;
-    int tile_base;              // first pixel tile of this launch (a launch may cover a tile range of the level: conv.hip tail split)
+    int tile_base;              // first pixel tile of this launch (0: a launch covers every tile of its levels)
     int part_pix0, part_rows;   // partial tiles: row r of split z lies at part + (z * part_rows + r - part_pix0) * Co
     const unsigned short *wf;   // weights in fragment order (conv_wfrag_kernel)
     int wf_bytes;
     // output placement: pixel (b, ho, wo) of the (Ho, Wo) grid is stored at (b, oy0 + ho * ostep, ox0 + wo * ostep) of an
     // (OH, OW) map.  ostep = 0: the dense case.  Used by the strided backward-data pass (one residue class per launch).
     int ostep, oy0, ox0, OH, OW;
-    // ---- work distribution (conv.hip sk_plan).  The grid is one-dimensional in x: workgroups [0, n_dp) take one whole
+    // ---- work distribution (conv_route.h sk_pieces).  The grid is one-dimensional in x: workgroups [0, n_dp) take one whole
     // (pixel tile, column block) each; workgroups [n_dp, n_dp + sk_n) share the remaining sk_tiles tiles EVENLY BY CHUNKS
     // ("stream-K"): piece s owns the chunk units [U s / sk_n, U (s + 1) / sk_n) of the tile-major unit space, U = sk_tiles *
     // (chunks per tile).  A piece that covers only part of a tile leaves its accumulators in slot 2 s (the segment that
@@ -77,9 +77,9 @@ struct TapSub {
     int i0, istep, ni, j0, jstep, nj, kw;
 };
 
-__host__ __device__ inline int cv_ncc(int C) { return (C + 31) / 32; }
+__host__ __device__ constexpr int cv_ncc(int C) { return (C + 31) / 32; }
 // 32-channel output tiles of the weight image, padded with zero tiles to the width of the workgroup tile that serves
-// this Co (conv.hip conv_forward: 32, 64 or 128 columns): the scalar part of a buffer address is not range-checked, so
+// this Co (conv_route.h conv_route: 32, 64 or 128 columns): the scalar part of a buffer address is not range-checked, so
 // every tile a wave may ask for has to exist.
 __host__ __device__ inline int cv_nt(int Co) { return Co <= 32 ? 1 : Co <= 64 ? 2 : (Co + 127) / 128 * 4; }
 // bytes of the fragment-order image of a (Co, Kd, C) weight
@@ -230,7 +230,7 @@ __device__ __forceinline__ bf16x8 cv_load_frag(__amdgpu_buffer_rsrc_t rs, int vo
 // For the backward-data GEMM of the deformable family (conv_mm_rows: N = K C = 2304 columns, plain stores, no epilogue
 // terms), whose lane-per-pixel stores -- 32-byte pieces of 64 different rows per instruction -- made the L2 fetch every
 // partially written line: 0.68 GB fetched by a kernel that reads 27 MB (profiles/r3_pmc_hbm.txt).
-// SK: the launch has stream-K pieces (ConvArgs; conv.hip sk_plan).  A template parameter because the segment loop costs the
+// SK: the launch has stream-K pieces (ConvArgs; conv_route.h sk_pieces).  A template parameter because the segment loop costs the
 // plain form ~30 spilled scalar registers and 15 - 25 % on the shortest launches (profiles/r5_sk_sc1.txt).
 template <int TM, int TN, int WM, int WN, int NP, bool UNAL = false, bool FINE = false, bool TRANS = false, bool SK = false>
 __global__ __launch_bounds__(256, 2) void conv_mm_kernel(const ConvArgs a)

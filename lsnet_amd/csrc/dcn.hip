@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "conv_route.h"
 #include "dcn_kernels.h"
 #include "dcn_mm_kernels.h"
 #include "dcn_grouped_kernels.h"
@@ -272,34 +273,12 @@ static bool mm_bwd_ok(const DcnArgs &a)
     return fits_i32((int64_t)wb) && wb <= (size_t)8 * a.Co * a.kh * a.kw * a.C;
 }
 
-// Work distribution of a forward launch (dcn_mm_kernels.h DcnSk).  The chip holds 512 workgroups of the kernel; whole rounds
-// stay one workgroup per tile, the chunks of the r tiles of the last round are spread evenly over min(chunks / 4, cap) pieces
-// per tile (cap: 4 in a launch of at most one round, 16 in a longer one) and at most 512 pieces in all, one workgroup each: a
-// piece has about 4 chunks or more, with no guaranteed minimum (chunks / 4 rounds down).  Measured
-// (tools/ubench/dcn_step, LSN_DBG_FWD_SK_NEVER = whole tiles only, profiles/r6_dcn_sk.txt): the pyramid launch
-// (2 100 tiles: four rounds and 52 tiles) 780 -> 759 us; the tower launch (700 tiles: one round and 188 tiles) 278 -> 283 us --
-// its second round runs one workgroup per CU, which has the matrix pipe to itself and finishes in ~0.65 of a round, so the
-// even split has little to return and the pieces' table rebuild and hand-over cost more.  Hence: launches of two rounds and
-// more only (the opposite of the dense kernel's rule, conv.hip sk_plan, whose short tiles lose to the longer prologue there).
-static void dcn_sk_plan(int ntw, int Tall, DcnSk *sk)
+// Work distribution of a forward launch (dcn_mm_kernels.h DcnSk): the stream-K pieces of conv_route.h under the deformable
+// forward's own admission rule (sk_admit_dcn_fwd, with its measurements).
+static DcnSk dcn_fwd_sk(int ntw, int Tall)
 {
-    sk->n_dp = ntw, sk->sk_n = 0, sk->sk_tiles = 0, sk->part = nullptr, sk->cnt = nullptr;
-    constexpr int SLOTS = 512;
-    const bool forced = dbg_on(LSN_DBG_FWD_SK_ALWAYS);   // pieces for launches of any size (tests)
-    // launches of less than HALF a round (a backbone layer of configs 3 / 4: 8 400 pixels = 132 tiles, 2 100 = 33) leave most
-    // of the chip idle as whole tiles: up to four pieces per tile (the dense kernel's rule); between half a round and two
-    // rounds (the tower launch) whole tiles win, see above
-    if (dbg_on(LSN_DBG_FWD_SK_NEVER) || Tall < 8 || (ntw >= SLOTS / 2 && ntw < 2 * SLOTS && !forced)) return;
-    const int r = ntw % SLOTS;
-    if (r == 0 || r > 448) return;
-    int per_tile = Tall / 4;
-    const int cap = ntw > SLOTS ? 16 : 4;
-    if (per_tile > cap) per_tile = cap;
-    const long long pieces = (long long)r * per_tile;
-    const int ns = pieces < SLOTS ? (int)pieces : SLOTS;
-    if (ns <= r) return;
-    if (r > SK_MAX_TILES || ((long long)r * Tall + 1) * ns >= ((long long)1 << 31)) return;
-    sk->n_dp = ntw - r, sk->sk_n = ns, sk->sk_tiles = r;
+    const SkPieces p = sk_pieces(ntw, Tall, sk_admit_dcn_fwd(ntw, dbg_on(LSN_DBG_FWD_SK_ALWAYS), dbg_on(LSN_DBG_FWD_SK_NEVER)));
+    return DcnSk{p.n_dp, p.sk_n, p.sk_tiles, nullptr, nullptr};
 }
 
 template <int TM, int TN, int WM, int WN, int NP, bool FINE = false>
@@ -308,8 +287,7 @@ static int launch_fwd_mm_cfg(const DcnArgs &a, hipStream_t st)
     constexpr int BN = WN * TN * 32;
     const size_t lds = dcn_fwd_mm_lds_bytes(SplitCfg<NP>::NPL, a.kh * a.kw * a.dg);
     const int blocks = a.ntiles * (a.Co / BN);
-    DcnSk sk;
-    dcn_sk_plan(blocks, a.kh * a.kw * (a.C / 32), &sk);
+    DcnSk sk = dcn_fwd_sk(blocks, a.kh * a.kw * (a.C / 32));
     if (!sk.sk_n) return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, false>, dim3(blocks), lds, st, a, a.wtp, a.wtp_bytes, sk);
     if (int rc = stream_sk_scratch((size_t)2 * sk.sk_n * 64 * BN, &sk.part, &sk.cnt, st)) return rc;
     return launch256(dcn_fwd_mm_kernel<TM, TN, WM, WN, NP, FINE, true>, dim3(sk.n_dp + sk.sk_n), lds, st, a, a.wtp, a.wtp_bytes, sk);

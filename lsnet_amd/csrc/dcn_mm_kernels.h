@@ -30,7 +30,7 @@ struct __align__(16) FTap {
 
 __host__ __device__ inline size_t dcn_fwd_mm_lds_bytes(int npl, int KD) { return (size_t)2 * npl * 64 * 64 + (size_t)64 * KD * sizeof(FTap); }
 
-// Work distribution of a forward launch (dcn.hip dcn_sk_plan), the scheme of conv_kernels.h: workgroups [0, n_dp) take one whole
+// Work distribution of a forward launch (conv_route.h sk_pieces), the scheme of conv_kernels.h: workgroups [0, n_dp) take one whole
 // (pixel tile, column block) each; workgroups [n_dp, n_dp + sk_n) share the LAST sk_tiles tiles evenly by chunks.  A tower
 // launch of the LSNet step has 700 tiles for 512 resident workgroups (two rounds, the second 37 % full), a pyramid launch 2 100
 // (five rounds, the last 10 % full).  A piece that holds part of a tile's sum leaves its accumulators in a slot, draws a ticket,

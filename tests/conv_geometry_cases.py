@@ -8,7 +8,7 @@ counts around the kernels' 4- and 8-channel granularities, and the row-merged fo
 
 Sizes: the smallest at which a launch still has two pixel tiles with a ragged last one -- input AND output at least
 9 x 11 at B = 3 (297 pixels: three 128-pixel tiles, five 64-pixel ones) -- so that the whole table costs seconds.  Every
-geometry of groups 1 .. 6 meets the four forward tiles of csrc/conv.hip conv_forward (Co <= 32, <= 64, wider, Co % 256 == 0)
+geometry of groups 1 .. 6 meets the four forward tiles of csrc/conv_route.h conv_route (Co <= 32, <= 64, wider, Co % 256 == 0)
 through Co = 24, 48, 136, 256, with C alternating between 32 (one 32-channel chunk) and 72 (a partial third chunk); one row
 per group has C = 64, Co = 256 and >= 4096 output pixels, which is where csrc/conv_wgrad_route.h cw_dense_mm_ok takes the
 weight gradient of a kernel with nine taps or more (group 7 is about narrow channel counts and has no such row).

@@ -830,15 +830,19 @@ CONV_CASES = [
     (2, 64, 256, 3, 1, 1, 1, 48, 50, True),
     (1, 1024, 512, 1, 1, 0, 1, 50, 48, False),
     (2, 512, 256, 1, 2, 0, 1, 80, 84, True),
-    # 265 pixel tiles x 2 column blocks = 530 tiles on 512 workgroup slots under a deep reduction: all 530 are spread evenly by
-    # chunks over 512 workgroups (round 5, csrc/conv.hip sk_plan: stream-K pieces, last arriver of a tile adds its partial
-    # sums in chunk order), forward and data gradient
+    # The routes of the last four rows as csrc/conv_route.h gives them (tests/test_conv_route_host.py holds each of them).
+    # 265 pixel tiles x 2 column blocks = 530 tiles on 512 workgroup slots under a deep reduction: 512 whole tiles, and the 18
+    # tiles of the last round as stream-K pieces (the last arriver of a tile adds its partial sums in chunk order) -- 234
+    # pieces of the 64 x 256 tile's 54 chunks in the forward, 288 of the 64 x 128 tile's 144 chunks in the data gradient
     (1, 192, 512, 3, 1, 1, 1, 130, 130, True),
-    # the other seams of sk_plan: whole tiles in front of the stream-K part (1048 tiles: 512 plain + 536 shared), few tiles
-    # under a deep reduction (66 tiles, 144 chunks: 512 pieces of ~18 chunks, up to nine partial sums per tile), a strided
-    # data gradient whose residue classes take stream-K pieces with an output step, and pieces over levels of unequal size
+    # two whole rounds and more get no pieces: 1048 whole tiles of 64 x 256 in the forward; its data gradient (512 -> 64: the
+    # 128 x 64 tile) is 262 tiles, all of them as 512 pieces
     (1, 64, 512, 3, 1, 1, 1, 184, 182, False),
+    # few tiles under a deep reduction: 66 tiles of 64 x 256 under 144 chunks take 7 blockIdx.z splits and the reduce launch,
+    # forward and data gradient
     (2, 512, 512, 3, 1, 1, 1, 25, 42, True),
+    # a strided data gradient whose residue classes take stream-K pieces with an output step: 132 tiles of 64 x 256 (the class
+    # of one tap: 264 of 64 x 128) as 512 pieces each; the forward likewise
     (2, 256, 256, 3, 2, 1, 1, 100, 168, False),
 ]
 
@@ -1023,12 +1027,19 @@ def test_conv2d_multi_level_equals_single(C, Co, k, bias, relu, split_mode):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('C,Co,k,s,H,W', [(512, 512, 3, 1, 25, 42), (256, 256, 3, 1, 50, 84), (192, 512, 3, 1, 130, 130),
-                                          (256, 256, 3, 2, 100, 168)])
+@pytest.mark.parametrize('C,Co,k,s,H,W', [
+    (512, 512, 3, 1, 25, 42),     # no stream-K: 66 tiles under 144 chunks take 7 blockIdx.z splits + the reduce launch, both passes
+    (256, 256, 3, 1, 50, 84),     # 132 tiles of 64 x 256 as 512 pieces, both passes
+    (192, 512, 3, 1, 130, 130),   # no stream-K: 1058 tiles are two rounds and more -- whole tiles, both passes
+    (256, 256, 3, 2, 100, 168),   # 512 pieces in the forward and in each residue class of the data gradient (an output step)
+    (192, 512, 3, 1, 92, 92),     # 530 tiles: 512 whole tiles in front of 18 tiles as 234 (data gradient: 288) pieces
+])
 def test_conv2d_stream_k_is_deterministic(C, Co, k, s, H, W):
-    """Stream-K launches (csrc/conv.hip sk_plan) add a tile's partial sums in chunk order whichever workgroup arrives last:
-    the same bits on every run, forward and data gradient, and the arrival counters are left re-armed (the second and third
-    calls would hang short of a tile or double-count otherwise)."""
+    """Every work distribution of csrc/conv_route.h gives the same bits on every run, forward and data gradient.  Stream-K
+    launches (sk_pieces) add a tile's partial sums in chunk order whichever workgroup arrives last, and leave the arrival
+    counters re-armed (the second and third calls would hang short of a tile or double-count otherwise); the blockIdx.z split
+    adds its partial tiles in a reduce launch; whole tiles have nothing to add.  The route of each row (stated beside it, at
+    this test's B = 2) is a row of tests/test_conv_route_host.py."""
     from lsnet_amd.ops.conv import conv2d
     torch.manual_seed(11)
     dev = _dev()

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 _CL = torch.channels_last
 LSN_ERR_RUNTIME = -3
-# B, C, H, W, Co of the two 3x3 convolutions (csrc/conv.hip sk_plan / z_split as they stand):
+# B, C, H, W, Co of the two 3x3 convolutions (csrc/conv_route.h; both are rows of tests/test_conv_route_host.py):
 #   Z_SPLIT: one 128 x 64 tile under 72 chunks -> 9 blockIdx.z splits + the reduce launch (data gradient: 2 splits)
 #   STREAM_K: 130 tiles of 64 x 128 under 18 chunks -> 512 stream-K pieces over scratch + arrival counters (data gradient: 65
 #             tiles, 4 blockIdx.z splits)
