@@ -622,13 +622,13 @@ int lsn_debug_phase_clocks(long long *device_buf_512, int word);
 
 /* Per-kernel-family launch timing.  lsn_prof_enable(1) clears the log and makes every launch of the instrumented
  * families record a HIP event pair on its launch stream; lsn_prof_read() waits for the recorded events and returns one
- * entry per family -- dcn_fwd, dcn_bwd_data, dcn_wgrad, conv_fwd, conv_bwd_data, conv_wgrad, norm, gconv, decode -- with the
+ * entry per family -- dcn_fwd, dcn_bwd_data, dcn_wgrad, conv_fwd, conv_bwd_data, conv_wgrad, norm, gconv, decode, points -- with the
  * launch count, the summed kernel time and the summed ALGORITHMIC flops / bytes of those launches (contractions: 2 x
  * output pixels x Co x C/groups x kh x kw flops; bytes: each operand read or written once).
  * lsn_prof_enable(on): 0 = off, 1 = every family, any other value = a bit mask of families in the order above (bit 0 =
  * dcn_fwd ...), so that a timed run can carry the events of ONE family only (a few dozen launches per step) after a
  * warm-up run with all of them found out which one dominates.
- * Returns the number of entries written (9) or a negative lsn error.  Not thread-safe. */
+ * Returns the number of entries written (10) or a negative lsn error.  Not thread-safe. */
 typedef struct lsn_prof_entry {
     char name[48];
     long long launches;
@@ -921,6 +921,43 @@ int lsn_sep_focal_forward(int B, int C, int n_levels, const lsn_sem_level *level
                           lsn_stream_t stream);
 int lsn_sep_focal_backward(int B, int C, int n_levels, const lsn_sem_level *levels, const float *target, const float *weight,
                            int h, int w, float gamma, float alpha, const float *stats, const float *g, lsn_stream_t stream);
+
+/* ---- LSHead's point decoding (csrc/points.hip, arithmetic in csrc/point_rows.h) -------------------------------------------
+ * The pixel-wise statements between the head's 1x1 outputs and their consumers (ls_head.py: softplus, get_pred_reg, the
+ * gradient_mul mix, the base grid, the refine sum, the proposal boxes), with the rounding of the torch statements they
+ * replace.  All tensors are fp32 pixel rows with a row pitch in floats of their own (pitch >= width); 16-byte accesses are
+ * used only where every pointer is 16-byte aligned and every pitch a multiple of 4.  Every call is one launch on `stream`,
+ * allocates nothing, reads nothing back, uses no atomic operation and gives the same bits on every run.  Argument errors
+ * (NULL pointers, n_sp not a multiple of 4, a table entry outside the row, a pitch below the width) return LSN_ERR_INVALID
+ * before anything is launched.
+ *
+ * lsn_point_decode_forward: raw (rows x c_raw) -> sp (rows x n_sp) = softplus(raw[:n_sp]) (beta 1, threshold 20) and off
+ *   (rows x n_off).  src: HOST table of n_off <= 32 entries; src[j] >= 0 is the sp channel of a pair's neg half (even, pos
+ *   the next one) and gives s = pos > neg ? pos : -neg; src[j] < 0 names the free channel raw[n_sp - 1 - src[j]].  No two
+ *   entries may name the same source.  off[j] = (fl(fl(1 - gm) * s) + fl(gm * s)) - base[j] with 1 - gm formed in double and gm
+ *   itself rounded to fp32, as torch treats the Python scalars;
+ *   base: n_off floats in DEVICE memory.  c_raw <= 256.
+ * lsn_point_decode_backward: g_sp (rows x n_sp) and g_off (rows x n_off), either may be NULL, -> g_raw (rows x c_raw), every
+ *   element written: fl(gm * g_off[j]) goes to the winner of its pair (negated for neg), is added to g_sp and multiplied with
+ *   the softplus derivative of the saved raw (z = expf(x); x > 20 ? g : g * z / (z + 1)); a free channel gets
+ *   fl(gm * g_off[j]), a channel nothing reads 0.  sp: the forward's output.
+ * lsn_softplus_add_forward / _backward: y = softplus(fl(a + b)) over rows x C; the gradient of a (b is detached) from the
+ *   sum formed again.
+ * lsn_point_boxes: rows (B * n_all x C) of softplus halves, points (n_all, 3) = x, y, stride -> out (B * n_all x 4).  mode 0
+ *   (extreme): [x of landmark 1, y of landmark 0, x of landmark 3, y of landmark 2] of the signed pairs; mode 1 (vectors):
+ *   [min x, min y, max x, max y] over the first nv vectors (y = pair 2v, x = pair 2v + 1).  out = point xy + fl(box * stride). */
+int lsn_point_decode_forward(const float *raw, int raw_pitch, int c_raw, int n_sp, const int *src, int n_off, double gradient_mul,
+                             const float *base, float *sp, int sp_pitch, float *off, int off_pitch, int64_t rows,
+                             lsn_stream_t stream);
+int lsn_point_decode_backward(const float *raw, int raw_pitch, int c_raw, int n_sp, const int *src, int n_off, double gradient_mul,
+                              const float *sp, int sp_pitch, const float *g_sp, int gsp_pitch, const float *g_off, int goff_pitch,
+                              float *g_raw, int graw_pitch, int64_t rows, lsn_stream_t stream);
+int lsn_softplus_add_forward(const float *a, int a_pitch, const float *b, int b_pitch, float *y, int y_pitch, int C, int64_t rows,
+                             lsn_stream_t stream);
+int lsn_softplus_add_backward(const float *a, int a_pitch, const float *b, int b_pitch, const float *grad_y, int gy_pitch,
+                              float *grad_a, int ga_pitch, int C, int64_t rows, lsn_stream_t stream);
+int lsn_point_boxes(const float *rows, int pitch, int C, const float *points, int n_all, int B, int mode, int nv, float *out,
+                    int out_pitch, lsn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -248,6 +248,11 @@ def _signatures():
         'lsn_sep_focal_workspace_bytes': (q, [i, i, i, P(SemLevel)]),
         'lsn_sep_focal_forward': (i, [i, i, i, P(SemLevel), p, p, i, i, f, f] + [p] * 4),
         'lsn_sep_focal_backward': (i, [i, i, i, P(SemLevel), p, p, i, i, f, f, p, p, p]),
+        'lsn_point_decode_forward': (i, [p, i, i, i, p, i, d, p, p, i, p, i, q, p]),
+        'lsn_point_decode_backward': (i, [p, i, i, i, p, i, d, p, i, p, i, p, i, p, i, q, p]),
+        'lsn_softplus_add_forward': (i, [p, i, p, i, p, i, i, q, p]),
+        'lsn_softplus_add_backward': (i, [p, i, p, i, p, i, p, i, i, q, p]),
+        'lsn_point_boxes': (i, [p, i, i, p, i, i, i, i, p, i, p]),
     }
 
 
@@ -282,7 +287,8 @@ def check(rc):
         raise RuntimeError(msg)
 
 
-PROF_FAMILIES = ('dcn_fwd', 'dcn_bwd_data', 'dcn_wgrad', 'conv_fwd', 'conv_bwd_data', 'conv_wgrad', 'norm', 'gconv', 'decode')
+PROF_FAMILIES = ('dcn_fwd', 'dcn_bwd_data', 'dcn_wgrad', 'conv_fwd', 'conv_bwd_data', 'conv_wgrad', 'norm', 'gconv', 'decode',
+                 'points')
 
 
 def prof_enable(on, families=None):

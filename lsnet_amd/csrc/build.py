@@ -7,8 +7,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, 'liblsnet_hip.so')
-SOURCES = ['lib_state.hip', 'dcn.hip', 'misc.hip', 'norm.hip', 'conv.hip', 'gconv.hip', 'image.hip', 'loss.hip', 'assign.hip', 'pool.hip', 'decode.hip', 'cpv.hip']
-HEADERS = ['common.h', 'lib_state.h', 'per_stream.h', 'conv_wgrad_route.h', 'conv_route.h', 'dcn_kernels.h', 'dcn_gather_kernels.h', 'dcn_sort_plan.h', 'dcn_grouped_kernels.h', 'conv_kernels.h', 'conv_wgrad_kernels.h', 'dcn_mm_kernels.h', 'prof.h', 'cross_iou_row.h', 'assign_rows.h', 'pool_rows.h', 'decode_rows.h', 'cpv_rows.h', os.path.join('..', '..', 'include', 'lsnet_hip.h')]
+SOURCES = ['lib_state.hip', 'dcn.hip', 'misc.hip', 'norm.hip', 'conv.hip', 'gconv.hip', 'image.hip', 'loss.hip', 'assign.hip', 'pool.hip', 'decode.hip', 'cpv.hip', 'points.hip']
+HEADERS = ['common.h', 'lib_state.h', 'per_stream.h', 'conv_wgrad_route.h', 'conv_route.h', 'dcn_kernels.h', 'dcn_gather_kernels.h', 'dcn_sort_plan.h', 'dcn_grouped_kernels.h', 'conv_kernels.h', 'conv_wgrad_kernels.h', 'dcn_mm_kernels.h', 'prof.h', 'cross_iou_row.h', 'assign_rows.h', 'pool_rows.h', 'decode_rows.h', 'cpv_rows.h', 'point_rows.h', os.path.join('..', '..', 'include', 'lsnet_hip.h')]
 # -fno-slp-vectorize: hipcc (ROCm 7.2) packs adjacent scalar fp32 adds / fmas into v_pk_add_f32 / v_pk_fma_f32.  In the
 # backward-data kernels the HIGH dword of such packed accumulators came back wrong for the last 16 lanes of a wave in
 # 0.7 % of the cases, differently on every run, whenever two workgroups shared a CU (tools/dbg_goff.py on the MI355X:
@@ -47,10 +47,13 @@ UNIT_HEADERS = {
     'gconv.hip': ['common.h', 'prof.h'],
     'image.hip': ['common.h'], 'loss.hip': ['common.h', 'cross_iou_row.h'], 'assign.hip': ['common.h', 'assign_rows.h'],
     'pool.hip': ['common.h', 'pool_rows.h'], 'decode.hip': ['common.h', 'decode_rows.h', 'pool_rows.h', 'prof.h'], 'cpv.hip': ['common.h', 'assign_rows.h', 'cpv_rows.h'],
+    'points.hip': ['common.h', 'point_rows.h', 'prof.h'],
 }
-# flags of single translation units, after FLAGS: target assignment, the detection decode and the corner-verification targets
-# and losses are separately rounded fp32 arithmetic (assign_rows.h, decode_rows.h, cpv_rows.h)
-UNIT_FLAGS = {'assign.hip': ['-ffp-contract=off'], 'decode.hip': ['-ffp-contract=off'], 'cpv.hip': ['-ffp-contract=off']}
+# flags of single translation units, after FLAGS: target assignment, the detection decode, the corner-verification targets
+# and losses and the head's point decoding are separately rounded fp32 arithmetic (assign_rows.h, decode_rows.h, cpv_rows.h,
+# point_rows.h)
+UNIT_FLAGS = {'assign.hip': ['-ffp-contract=off'], 'decode.hip': ['-ffp-contract=off'], 'cpv.hip': ['-ffp-contract=off'],
+              'points.hip': ['-ffp-contract=off']}
 API_HEADER = os.path.join('..', '..', 'include', 'lsnet_hip.h')
 
 

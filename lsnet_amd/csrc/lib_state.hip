@@ -45,7 +45,7 @@ int math_np()
 
 // ---- per-kernel launch timing (prof.h) ----
 static const char *const kProfNames[PROF_N] = {"dcn_fwd", "dcn_bwd_data", "dcn_wgrad", "conv_fwd", "conv_bwd_data",
-                                               "conv_wgrad", "norm", "gconv", "decode"};
+                                               "conv_wgrad", "norm", "gconv", "decode", "points"};
 static unsigned g_prof_mask = 0;   // bit f: family f records events
 static std::vector<ProfRec> g_prof;
 bool prof_on(int fam) { return fam >= 0 && fam < 32 && ((g_prof_mask >> fam) & 1u); }

@@ -18,7 +18,8 @@ enum {
     PROF_NORM = 6,        // frozen-BN + add + ReLU and GroupNorm passes (HBM-bound streaming kernels)
     PROF_GCONV = 7,       // grouped conv (ResNeXt)
     PROF_DECODE = 8,      // detection decode (select, candidates, sort + NMS: three launches per batch)
-    PROF_N = 9
+    PROF_POINTS = 9,      // LSHead's point decoding (point decode, softplus-add, point boxes: one launch per call)
+    PROF_N = 10
 };
 
 struct ProfRec {

@@ -32,6 +32,7 @@ from ...ops.backend import get_backend
 from ...ops import ModulatedDeformConvPack, PyramidDeformConv
 from ...ops.dcn import offset_scale_chain
 from ...ops import cross_iou as fused_ciou
+from ...ops import point_decode as point_ops
 from ...ops.focal import level_rows_ok, level_sums
 from ...ops.streams import side_stream
 from ..builder import HEADS, build_loss
@@ -296,6 +297,24 @@ class LSHead(nn.Module):
             self._consts[key] = t
         return t
 
+    def _base_offset(self, like):
+        """The base grid (1, 2*taps, 1, 1) in `like`'s dtype, converted once per (device, dtype) instead of in every forward."""
+        key = ('base_offset', like.device, like.dtype)
+        t = self._consts.get(key)
+        if t is None or t[0] is not self.dcn_base_offset:       # (the buffer is replaced when the module moves)
+            t = self._consts[key] = (self.dcn_base_offset, self.dcn_base_offset.type_as(like).contiguous())
+        return t[1]
+
+    def _offset_sources(self, branch):
+        """Where the sampling offsets of a branch come from in its init output (ops/point_decode.py: offset_sources): the
+        selection `get_pred_reg` makes, as the table the library takes."""
+        key = ('offset_sources', branch)
+        t = self._consts.get(key)
+        if t is None:
+            d_init, n_sp = self._out_dims(branch)
+            t = self._consts[key] = point_ops.offset_sources(self.task, n_sp, d_init, self.num_kernel_points)
+        return t
+
     @staticmethod
     def _level_list(lvl, num_levels):
         if lvl == 0:
@@ -349,7 +368,7 @@ class LSHead(nn.Module):
         convolutions (forward_train starts the refine-stage assignment there, on its second stream)."""
         nl = len(feats)
         shapes = [tuple(f.shape[2:]) for f in feats]
-        base_offset = self.dcn_base_offset.type_as(feats[0])
+        base_offset = self._base_offset(feats[0])
         cls_feats = self._run_tower(self.cls_convs, feats)
         st = {}
         for b in self.branches:
@@ -358,11 +377,15 @@ class LSHead(nn.Module):
             n_sp = self._out_dims(b)[1]
             # 3x3 conv per level; everything after it is pixel-wise: one pass over the concatenated levels
             raw = init_out(self._cat_px(init_conv.forward_multi(tower, relu=True)))   # (ReLU in the 3x3 launch's epilogue)
-            sp = self.softplus(raw[:, :n_sp])
-            reg = self.get_pred_reg(sp, raw[:, n_sp:] if raw.shape[1] > n_sp else None)
-            reg = (1 - self.gradient_mul) * reg.detach() + self.gradient_mul * reg
-            st[b] = dict(feat=tower, sp_all=sp, sp=self._split_px(sp, shapes),
-                         off=self._split_px(reg - base_offset, shapes))
+            if point_ops.native_ok(raw):
+                # (default; LSNET_NATIVE_POINTS=0 switches it off) the statements below as one launch each way
+                sp, off = point_ops.point_decode(raw, n_sp, self._offset_sources(b), self.gradient_mul, base_offset)
+            else:
+                sp = self.softplus(raw[:, :n_sp])
+                reg = self.get_pred_reg(sp, raw[:, n_sp:] if raw.shape[1] > n_sp else None)
+                reg = (1 - self.gradient_mul) * reg.detach() + self.gradient_mul * reg
+                off = reg - base_offset
+            st[b] = dict(feat=tower, sp_all=sp, sp=self._split_px(sp, shapes), off=self._split_px(off, shapes))
 
         if after_init is not None:
             after_init({b: st[b]['sp'] for b in self.branches})
@@ -416,7 +439,11 @@ class LSHead(nn.Module):
             af, fc = getattr(self, f'{b}_af_dcn_conv'), getattr(self, f'{b}_feat_conv')
             gn, ro = getattr(self, f'{b}_GN'), getattr(self, f'pts_{b}_refine_out')
             fused = fuse(af, fc, raw, st[b]['feat'])
-            refine = self.softplus(ro(self._gn_cat(gn, fused)) + st[b]['sp_all'].detach())
+            ref_raw, sp_init = ro(self._gn_cat(gn, fused)), st[b]['sp_all'].detach()
+            if point_ops.native_ok(ref_raw, sp_init):
+                refine = point_ops.softplus_add(ref_raw, sp_init)
+            else:
+                refine = self.softplus(ref_raw + sp_init)
             outs[b] = self._split_px(refine, shapes)
 
         none = [None] * nl
@@ -444,7 +471,9 @@ class LSHead(nn.Module):
             def hook(init_preds):
                 side.wait_stream(main)                  # the init predictions are main-stream work
                 with torch.cuda.stream(side):
-                    stage2.append(self.refine_stage_targets(pre, [p.detach() for p in init_preds[self._box_branch()]]))
+                    # (the views themselves, not detached copies: they carry the tag of the tensor they are views of, and
+                    # refine_stage_targets detaches what it reads)
+                    stage2.append(self.refine_stage_targets(pre, init_preds[self._box_branch()]))
         outs = self(x, after_init=hook)
         if pre is not None:
             # (no record_stream: the next use of the side stream starts with wait_stream(main) again, i.e. behind every reader of
@@ -735,7 +764,8 @@ class LSHead(nn.Module):
         tg_init, n_init = self.get_targets([flat_points] * num_imgs, flat_flags, all_valid, num_level, gt_bboxes,
                                            gt_labels, extra, 'init')
         return dict(featmap_sizes=featmap_sizes, extra=extra, gt_bboxes=gt_bboxes, gt_labels=gt_labels, points=points,
-                    all_valid=all_valid, num_level=num_level, flat_flags=flat_flags, tg_init=tg_init, n_init=n_init)
+                    flat_points=flat_points, all_valid=all_valid, num_level=num_level, flat_flags=flat_flags, tg_init=tg_init,
+                    n_init=n_init)
 
     def _box_branch(self):
         return 'bbox' if 'bbox' in self.branches else self.branches[0]
@@ -745,14 +775,21 @@ class LSHead(nn.Module):
         (lsnet_head.py:1342-1378).  Returns (targets, positive count)."""
         points, box_branch = init_stage['points'], self._box_branch()
         num_imgs = init_preds[0].shape[0]
-        decoded = []
-        for lvl, p in enumerate(init_preds):
-            p = p.detach()
-            box = self.extreme_points2bbox(p) if box_branch == 'bbox' else self.vectors2bbox(p)
-            box = box * self.point_strides[lvl]
-            centre = torch.cat([points[lvl][:, :2], points[lvl][:, :2]], dim=1)
-            decoded.append(centre[None] + box.permute(0, 2, 3, 1).reshape(num_imgs, -1, 4))
-        boxes = torch.cat(decoded, dim=1)
+        rows = self._px_base(init_preds)
+        flat_points = init_stage.get('flat_points')
+        if rows is not None and flat_points is not None and point_ops.boxes_ok(rows, flat_points):
+            # (default; LSNET_NATIVE_POINTS=0 switches it off) the statements below for all levels in one launch
+            boxes = point_ops.point_boxes(rows, flat_points, 'extreme' if box_branch == 'bbox' else 'vectors',
+                                          rows.shape[2] // 4 - 1)
+        else:
+            decoded = []
+            for lvl, p in enumerate(init_preds):
+                p = p.detach()
+                box = self.extreme_points2bbox(p) if box_branch == 'bbox' else self.vectors2bbox(p)
+                box = box * self.point_strides[lvl]
+                centre = torch.cat([points[lvl][:, :2], points[lvl][:, :2]], dim=1)
+                decoded.append(centre[None] + box.permute(0, 2, 3, 1).reshape(num_imgs, -1, 4))
+            boxes = torch.cat(decoded, dim=1)
         return self.get_targets([boxes[i] for i in range(num_imgs)], init_stage['flat_flags'], init_stage['all_valid'],
                                 init_stage['num_level'], init_stage['gt_bboxes'], init_stage['gt_labels'], init_stage['extra'],
                                 'refine', stacked=boxes)

@@ -669,6 +669,88 @@ class HipBackend:
         _lib.check(lib.lsn_dense_targets(ptr(gt_inds), P, ptr(table), D, ptr(out), stream()))
         return out
 
+    # ------------------------------------------------------------------ LSHead's point decoding (csrc/points.hip)
+    _point_tables = {}
+
+    @classmethod
+    def _point_table(cls, picks):
+        """the host table of offset sources as the C ABI takes it (kept: the same few tuples come back every step)"""
+        t = cls._point_tables.get(picks)
+        if t is None:
+            t = cls._point_tables[picks] = (ctypes.c_int * len(picks))(*picks)
+        return t
+
+    @staticmethod
+    def _point_rows(t, what, width=None):
+        from .point_decode import row_layout
+        lay = row_layout(t) if t.dtype == torch.float32 and t.is_cuda else None
+        if lay is None:
+            raise ValueError(f'{what}: {tuple(t.shape)} {t.dtype} with strides {t.stride()} is not a tensor of fp32 pixel rows')
+        pitch, rows, C = lay
+        if width is not None and C != width:
+            raise ValueError(f'{what} has rows of {C} floats, expected {width}')
+        return ptr(t), pitch, rows, C
+
+    def point_decode_forward(self, raw, n_sp, picks, gradient_mul, base):
+        """raw: pixel rows of c_raw floats -> (sp, off) in raw's form (ops/point_decode.py says which forms there are)."""
+        from .point_decode import rows_like
+        lib = _lib.load()
+        rp, rpitch, rows, c_raw = self._point_rows(raw, 'raw')
+        n_off = len(picks)
+        if base.dtype != torch.float32 or base.device != raw.device or not base.is_contiguous() or base.numel() < n_off:
+            raise ValueError(f'base must hold {n_off} contiguous fp32 values on {raw.device}')
+        sp, off = rows_like(raw, n_sp), rows_like(raw, n_off)
+        _lib.check(lib.lsn_point_decode_forward(rp, rpitch, c_raw, n_sp, self._point_table(picks), n_off, float(gradient_mul),
+                                                ptr(base), ptr(sp), n_sp, ptr(off), n_off, rows, stream()))
+        return sp, off
+
+    def point_decode_backward(self, raw, sp, n_sp, picks, gradient_mul, g_sp, g_off):
+        """The gradient of raw, in raw's form; g_sp / g_off: pixel rows or None."""
+        from .point_decode import rows_like
+        lib = _lib.load()
+        rp, rpitch, rows, c_raw = self._point_rows(raw, 'raw')
+        n_off = len(picks)
+        sp_p, sp_pitch = self._point_rows(sp, 'sp', n_sp)[:2]
+        gs_p, gs_pitch = (None, n_sp) if g_sp is None else self._point_rows(g_sp, 'g_sp', n_sp)[:2]
+        go_p, go_pitch = (None, n_off) if g_off is None else self._point_rows(g_off, 'g_off', n_off)[:2]
+        g_raw = rows_like(raw, c_raw)
+        _lib.check(lib.lsn_point_decode_backward(rp, rpitch, c_raw, n_sp, self._point_table(picks), n_off, float(gradient_mul),
+                                                 sp_p, sp_pitch, gs_p, gs_pitch, go_p, go_pitch, ptr(g_raw), c_raw, rows, stream()))
+        return g_raw
+
+    def softplus_add_forward(self, a, b):
+        from .point_decode import rows_like
+        lib = _lib.load()
+        ap, apitch, rows, C = self._point_rows(a, 'a')
+        bp, bpitch = self._point_rows(b, 'b', C)[:2]
+        y = rows_like(a, C)
+        _lib.check(lib.lsn_softplus_add_forward(ap, apitch, bp, bpitch, ptr(y), C, C, rows, stream()))
+        return y
+
+    def softplus_add_backward(self, a, b, grad_y):
+        from .point_decode import rows_like
+        lib = _lib.load()
+        ap, apitch, rows, C = self._point_rows(a, 'a')
+        bp, bpitch = self._point_rows(b, 'b', C)[:2]
+        gp, gpitch = self._point_rows(grad_y, 'grad_y', C)[:2]
+        ga = rows_like(a, C)
+        _lib.check(lib.lsn_softplus_add_backward(ap, apitch, bp, bpitch, gp, gpitch, ptr(ga), C, C, rows, stream()))
+        return ga
+
+    POINT_BOX_MODES = {'extreme': 0, 'vectors': 1}
+
+    def point_boxes(self, rows, flat_points, mode, nv):
+        """rows (B, N, C), flat_points (N, 3) = x, y, stride -> (B, N, 4) proposal boxes."""
+        lib = _lib.load()
+        B, N, C = rows.shape
+        rp, rpitch = self._point_rows(rows, 'rows')[:2]
+        if flat_points.dtype != torch.float32 or tuple(flat_points.shape) != (N, 3) or not flat_points.is_contiguous():
+            raise ValueError(f'flat_points must be a contiguous fp32 ({N}, 3) tensor')
+        out = torch.empty((B, N, 4), dtype=torch.float32, device=rows.device)
+        _lib.check(lib.lsn_point_boxes(rp, rpitch, C, ptr(flat_points), N, B, self.POINT_BOX_MODES[mode], int(nv), ptr(out), 4,
+                                       stream()))
+        return out
+
     # ------------------------------------------------------------------ corner-point verification (csrc/cpv.hip)
     @staticmethod
     def _u8(valid, shape, dev):
