@@ -10,6 +10,7 @@
 #include "dcn_kernels.h"
 #include "dcn_mm_kernels.h"
 #include "dcn_grouped_kernels.h"
+#include "dcn_route.h"
 #include "lib_state.h"
 #include "prof.h"
 
@@ -136,11 +137,6 @@ static int i32(int64_t v, int *ok)
     return (int)v;
 }
 
-// 32-bit offsets: `elems` elements of `bytes_per` bytes stay below 2^31 (bytes_per = 1: a bound on the element count)
-static bool fits_i32(int64_t elems, int bytes_per = 1) { return elems * bytes_per < ((int64_t)1 << 31); }
-static int64_t in_elems(const DcnArgs &a, int i) { return (int64_t)a.lv[i].B * a.lv[i].H * a.lv[i].W * a.C; }
-static int64_t col_elems(const DcnArgs &a, int i) { return (int64_t)a.lv[i].P * a.kh * a.kw * a.C; }   // column-gradient rows
-
 template <typename KernelT>
 static int set_lds(KernelT kernel, size_t bytes)
 {
@@ -234,44 +230,8 @@ static int fill_levels(DcnArgs &a, const lsn_dcn_shape &s, int n, const lsn_dcn_
     return 0;
 }
 
-// VEC kernels need 16-byte aligned float4 rows: channel counts that are multiples of 4
-static bool vec_ok(const DcnArgs &a)
-{
-    const int Cg = a.C / a.groups, Cog = a.Co / a.groups;
-    return (Cg % 4 == 0) && (Cog % 4 == 0) && (a.Co % 4 == 0) && (a.SL % 4 == 0);
-}
-
-// ---- the kernels of dcn_mm_kernels.h (dense-convolution skeleton): conditions, weight image, launches ----
-static bool dcn_mm_env() { return !dbg_on(LSN_DBG_GENERAL_GEMMS); }   // (set: the kernels of dcn_kernels.h only -- tests, A/B runs)
-
-static bool mm_common_ok(const DcnArgs &a)
-{
-    if (math_np() == 0 || a.groups != 1 || a.dg < 1 || a.C % a.dg != 0 || !dcn_mm_env()) return false;
-    for (int i = 0; i < a.nlv; ++i)   // 32-bit buffer offsets
-        if (!fits_i32(in_elems(a, i), 4) || !fits_i32((int64_t)a.lv[i].P * a.opitch, 4)) return false;
-    return true;
-}
-
+// ---- the kernels of dcn_mm_kernels.h (dense-convolution skeleton): weight image, launches ----
 static int mm_npl() { return split_npl(math_np()); }
-
-static bool mm_fwd_ok(const DcnArgs &a)
-{
-    if (!mm_common_ok(a) || (a.C / a.dg) % 32 != 0 || a.Co % 128 != 0) return false;
-    if (dcn_fwd_mm_lds_bytes(mm_npl(), a.kh * a.kw * a.dg) > 80 * 1024) return false;
-    return fits_i32((int64_t)cv_wfrag_bytes(a.Co, a.kh * a.kw, a.C, mm_npl()));
-}
-
-// backward-data GEMM as a 1x1 convolution (conv.hip conv_mm_rows) + corner sums in the gather pass: every level that
-// wants offset / mask gradients must also want grad_input (its samples are then on the anchor lists); the fragment image
-// has to fit the caller's weight workspace (8 bytes per weight element, include/lsnet_hip.h)
-static bool mm_bwd_ok(const DcnArgs &a)
-{
-    if (!mm_common_ok(a) || a.C % 4 != 0 || a.Co % 4 != 0) return false;
-    for (int i = 0; i < a.nlv; ++i)
-        if ((a.lv[i].goff || a.lv[i].gmsk) && !a.lv[i].gx) return false;
-    const size_t wb = cv_wfrag_bytes(a.kh * a.kw * a.C, 1, a.Co, mm_npl());
-    return fits_i32((int64_t)wb) && wb <= (size_t)8 * a.Co * a.kh * a.kw * a.C;
-}
 
 // Work distribution of a forward launch (dcn_mm_kernels.h DcnSk): the stream-K pieces of conv_route.h under the deformable
 // forward's own admission rule (sk_admit_dcn_fwd, with its measurements).
@@ -306,41 +266,16 @@ static int launch_forward_mm(const DcnArgs &a, hipStream_t st)
 }
 
 template <int BM, int BN, int WM, int WN>
-static int launch_forward_t(const DcnArgs &a, hipStream_t st)
+static int launch_forward_t(const DcnArgs &a, bool vec, hipStream_t st)
 {
     const int Cog = a.Co / a.groups, KD = a.kh * a.kw * a.dg;
     const size_t lds = (size_t)(BM + BN) * 33 * 4 + (size_t)BM * KD * sizeof(Tap);
     dim3 grid(a.ntiles, cdiv(Cog, BN), a.groups);
-    return vec_ok(a) ? launch256(dcn_fwd_kernel<BM, BN, WM, WN, true>, grid, lds, st, a)
-                     : launch256(dcn_fwd_kernel<BM, BN, WM, WN, false>, grid, lds, st, a);
-}
-
-// the split one-workgroup-per-CU kernel (dcn_fwd_xn_kernel) needs float4 rows and 32-bit byte offsets into x and w
-static bool xn_ok(const DcnArgs &a)
-{
-    if (a.Co / a.groups <= 64 || !vec_ok(a)) return false;
-    if (!fits_i32((int64_t)a.Co * a.kh * a.kw * (a.C / a.groups), 4)) return false;
-    for (int i = 0; i < a.nlv; ++i)
-        if (!fits_i32(in_elems(a, i), 4)) return false;
-    return true;
+    return vec ? launch256(dcn_fwd_kernel<BM, BN, WM, WN, true>, grid, lds, st, a)
+               : launch256(dcn_fwd_kernel<BM, BN, WM, WN, false>, grid, lds, st, a);
 }
 
 // ---- grouped calls (dcn_grouped_kernels.h): ResNeXt's 64 groups of 8 / 16 / 32 channels ----
-static bool grouped_inputs_ok(const DcnArgs &a)   // 16-byte loads at 32-bit element offsets
-{
-    for (int i = 0; i < a.nlv; ++i)
-        if (!fits_i32(in_elems(a, i)) || (reinterpret_cast<uintptr_t>(a.lv[i].x) & 15) != 0) return false;
-    return true;
-}
-
-static bool grouped_fwd_ok(const DcnArgs &a)
-{
-    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C) return false;
-    const int cg = a.C / a.groups;
-    if (!(cg == 8 || cg == 16 || cg == 32) || a.C % GF_CH != 0 || a.C % a.dg != 0 || (a.C / a.dg) % GF_CH != 0) return false;
-    return dcn_fwd_grouped_lds_bytes(a.kh * a.kw) <= 64 * 1024 && grouped_inputs_ok(a);
-}
-
 static int launch_forward_grouped(const DcnArgs &a_in, hipStream_t st)
 {
     DcnArgs a = a_in;
@@ -356,10 +291,10 @@ static int launch_forward_grouped(const DcnArgs &a_in, hipStream_t st)
 }
 
 // exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU
-static int launch_forward_fp32(const DcnArgs &a, hipStream_t st)
+static int launch_forward_fp32(const DcnArgs &a, bool vec, hipStream_t st)
 {
     ProfScope prof(PROF_FWD, a, st);
-    return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, st) : launch_forward_t<64, 256, 1, 4>(a, st);
+    return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, vec, st) : launch_forward_t<64, 256, 1, 4>(a, vec, st);
 }
 
 // planes: a.wtp holds the weights as dcn_prepare_w_kernel split them; otherwise every block splits its own
@@ -375,326 +310,75 @@ static int launch_forward_xn(const DcnArgs &a, bool planes, hipStream_t st)
 }
 
 template <int RED>
-static int launch_bwd_data_t(const DcnArgs &a, hipStream_t st)
+static int launch_bwd_data_t(const DcnArgs &a, bool vec, hipStream_t st)
 {
     const int KD = a.kh * a.kw * a.dg;
     const size_t lds = (size_t)RED * 32 * 4 + (size_t)BWD_BM * KD * (sizeof(Tap) + 12);
-    return vec_ok(a) ? launch256(dcn_bwd_data_kernel<RED, true>, dim3(a.ntiles), lds, st, a)
-                     : launch256(dcn_bwd_data_kernel<RED, false>, dim3(a.ntiles), lds, st, a);
+    return vec ? launch256(dcn_bwd_data_kernel<RED, true>, dim3(a.ntiles), lds, st, a)
+               : launch256(dcn_bwd_data_kernel<RED, false>, dim3(a.ntiles), lds, st, a);
 }
 
-// 32-bit buffer offsets into the input and into every level's column-gradient rows (backward-data, every kernel in front
-// of the gather pass)
-static bool bwd_offsets_ok(const DcnArgs &a)
+// ---- the route of a call (dcn_route.h): the arguments as the shape the rule reads, and its plan as kernel arguments ----
+static_assert(DR_MAXLV == MAXLV && DR_GT == GT && DR_GF_CH == GF_CH && DR_GC_COLS == GC_COLS, "dcn_route.h plans for these kernels");
+static_assert(DR_WG_BP == WG_BP && DR_WG_BN == WG_BN && DR_WG_BM == WG_BM, "dcn_route.h counts the steps and tiles of these kernels");
+static_assert(DR_TAP_BYTES == sizeof(Tap) && DR_GENTRY_BYTES == sizeof(GEntry), "dcn_route.h sizes the tables of these kernels");
+
+static size_t gather_ws_bytes(const lsn_dcn_shape &s) { return (size_t)(s.gather_workspace_bytes > 0 ? s.gather_workspace_bytes : 0); }
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The only place that turns pointers into "present / aligned / shared" facts, and the only reader of the debug word and of the
+// math mode on behalf of the rule.  want_wgrad: grad_weight is asked for (backward; the queries answer for the case they name).
+static DcnRouteShape route_shape(const DcnArgs &a, const lsn_dcn_shape &s, lsn_layout layout, bool want_wgrad)
 {
-    for (int i = 0; i < a.nlv; ++i)
-        if (!fits_i32(in_elems(a, i), 4) || !fits_i32(col_elems(a, i), 4)) return false;
-    return true;
-}
-
-// round 2's split GEMM (dcn_bwd_data_xn_kernel) on the transposed weight planes the caller's `workspace` holds
-static bool bwd_x3_ok(const DcnArgs &a)
-{
-    if (math_np() == 0 || a.groups != 1) return false;
-    if (a.Co > 256 || a.Co % 8 != 0 || a.C % 4 != 0) return false;
-    if (!fits_i32((int64_t)a.kh * a.kw * a.C * a.Co, 6)) return false;
-    if (bwd_xn_lds_bytes(math_np(), a.kh * a.kw * a.dg) > 80 * 1024) return false;
-    return bwd_offsets_ok(a);
-}
-
-static bool bwd_colbuf_env() { return !dbg_on(LSN_DBG_ATOMIC_SCATTER); }   // (set: the atomic scatter kernels -- tests)
-
-// Exact-fp32 column gradients (dcn_gcol_grouped_kernel: fmaf chains per group) in front of the gather pass: grouped calls
-// (config 4: 64 groups) in every math mode, and -- round 6 -- EVERY call of LSN_MATH_FP32: the exact mode used to scatter
-// with fp32 atomics (round 1's kernels) and was the less reproducible, less exact of the modes; it now
-// shares the atomic-free, bit-reproducible gather with the default mode and differs from it in the GEMM arithmetic only.
-// Levels that want offset / mask gradients must want grad_input (anchor lists).
-static bool bwd_grouped_ok(const DcnArgs &a)
-{
-    if (a.groups <= 1 && math_np() != 0) return false;
-    if (a.C % a.groups != 0 || a.Co % a.groups != 0 || (a.C / a.groups) % 4 != 0 || a.C % a.dg != 0) return false;
-    if ((a.C / a.dg) % 4 != 0 || !bwd_colbuf_env()) return false;
-    for (int i = 0; i < a.nlv; ++i)
-        if ((a.lv[i].goff || a.lv[i].gmsk) && !a.lv[i].gx) return false;
-    return bwd_offsets_ok(a);
-}
-
-// ---- atomic-free grad_input: workspace plan of the list sort / gather sequence (dcn_gather_kernels.h) ----
-struct GatherPlan {
-    bool ok = false;
-    int nsamples = 0, nanchors = 0;
-    size_t o_gcol = 0, o_hist = 0, o_start = 0, o_key = 0, o_ent = 0, o_gtap = 0, bytes = 0;
-    size_t o_S = 0, o_H = 0, o_pairs = 0;
-    GatherArgs ga;        // groups gathered per 4x4 pixel block
-    AnchorArgs aa;        // groups with long lists: gathered per anchor (dcn_anchor_sum / combine)
-    int anchor_pixels = 0;
-    int na_long = 0;             // the first na_long anchors of the S buffer belong to long-list groups (4 waves each)
-    int64_t block_samples = 0;   // samples (upper bound) of the block-gathered groups
-};
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Fills prow0 / abase of the levels and the plan.  gx pointers: levels with the same grad_input share an anchor grid.
-// all_anchor: every group on the per-anchor path (route_backward says when).
-static void gather_plan(DcnArgs &a, GatherPlan &pl, bool all_anchor)
-{
-    pl.ok = false;
-    const int K = a.kh * a.kw, KD = K * a.dg;
-    int64_t prow = 0, anchors = 0, Q = 0;
-    GatherArgs &ga = pl.ga;
-    ga.ng = 0;
-    bool any = false;
-    int64_t gsamp[MAXLV] = {};   // samples (upper bound: every tap valid) that scatter into each group
+    DcnRouteShape r = {};
+    r.n = a.nlv;
     for (int i = 0; i < a.nlv; ++i) {
-        Lvl &L = a.lv[i];
-        L.prow0 = (int)prow;
-        prow += L.P;
-        L.abase = 0;
-        if (!L.gx) continue;
-        any = true;
-        int gi = -1;
-        for (int j = 0; j < ga.ng; ++j)
-            if (ga.g[j].gx == L.gx) gi = j;
-        if (gi < 0) {
-            gi = ga.ng++;
-            GatherGrp &G = ga.g[gi];
-            G.gx = L.gx, G.x = L.x, G.B = L.B, G.H = L.H, G.W = L.W;
-            G.abase = (int)anchors, G.blk0 = (int)Q;
-            anchors += (int64_t)L.B * (L.H + 1) * (L.W + 1);
-            Q += (int64_t)L.B * cdiv(L.H, GT) * cdiv(L.W, GT);
-        } else if (ga.g[gi].B != L.B || ga.g[gi].H != L.H || ga.g[gi].W != L.W) {
-            return;   // one buffer, two shapes: not a valid call for this path
-        }
-        L.abase = ga.g[gi].abase;
-        gsamp[gi] += (int64_t)L.P * KD;
+        const Lvl &L = a.lv[i];
+        DcnRouteLevel &R = r.lv[i];
+        R.B = L.B, R.H = L.H, R.W = L.W, R.Ho = L.Ho, R.Wo = L.Wo, R.P = L.P;
+        R.gx = L.gx != nullptr, R.goff = L.goff != nullptr, R.gmsk = L.gmsk != nullptr;
+        R.x_aligned16 = aligned16(L.x), R.gout_aligned16 = aligned16(L.gout);
+        R.gx_id = 0;
+        while (a.lv[R.gx_id].gx != L.gx) ++R.gx_id;   // the first level with this buffer (i at the latest)
     }
-    if (!any) return;
-    if (prow * KD >= ((int64_t)1 << 30) || anchors >= ((int64_t)1 << 30) || Q >= ((int64_t)1 << 30)) return;
-    if (a.C % 4 != 0 || (a.C / a.dg) % 4 != 0) return;
-    pl.nsamples = (int)(prow * KD);
-    pl.nanchors = (int)anchors;
-    if (ds_digit_bits(pl.nanchors) > DS_MAX_DIGIT_BITS) return;   // (cannot happen below 2^30 anchors: the LDS of the list sort)
-    // Groups with more than ~400 samples per 4x4 pixel block go to the per-anchor gather (the pyramid op's coarse source
-    // levels); the others keep the block walk.
-    constexpr int anchor_thr = 400;
-    AnchorArgs &aa = pl.aa;
-    aa.ng = 0, aa.NA = 0;
-    pl.anchor_pixels = 0, pl.block_samples = 0;
-    {
-        // anchor path: every group when the unweighted-GEMM pipeline can serve the call (its corner sums are cheapest per
-        // anchor), otherwise the groups above the threshold.  Long-list groups first: they get four waves per anchor.
-        GatherGrp keep[MAXLV];
-        bool to_anchor[MAXLV], is_long[MAXLV];
-        int nk = 0;
-        int64_t q = 0;
-        for (int j = 0; j < ga.ng; ++j) {
-            const GatherGrp &G = ga.g[j];
-            const int64_t nblk = (int64_t)G.B * cdiv(G.H, GT) * cdiv(G.W, GT);
-            const int64_t nanch = (int64_t)G.B * (G.H + 1) * (G.W + 1);
-            to_anchor[j] = all_anchor || (anchor_thr > 0 && gsamp[j] > (int64_t)anchor_thr * nblk);
-            constexpr int long_thr = 40;
-            is_long[j] = !all_anchor || gsamp[j] > (int64_t)long_thr * nanch;   // mean list length (upper bound)
-        }
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int j = 0; j < ga.ng; ++j) {
-                const GatherGrp &G = ga.g[j];
-                if (!to_anchor[j] || is_long[j] != (pass == 0)) continue;
-                AnchorGrp &A = aa.g[aa.ng++];
-                A.gx = G.gx, A.x = G.x, A.B = G.B, A.H = G.H, A.W = G.W, A.abase = G.abase, A.a0 = aa.NA;
-                aa.NA += G.B * (G.H + 1) * (G.W + 1);
-                pl.anchor_pixels += G.B * G.H * G.W;
-            }
-            if (pass == 0) pl.na_long = aa.NA;
-        }
-        for (int j = 0; j < ga.ng; ++j) {
-            if (to_anchor[j]) continue;
-            const GatherGrp &G = ga.g[j];
-            keep[nk] = G;
-            keep[nk].blk0 = (int)q;
-            q += (int64_t)G.B * cdiv(G.H, GT) * cdiv(G.W, GT);
-            pl.block_samples += gsamp[j];
-            ++nk;
-        }
-        for (int j = 0; j < nk; ++j) ga.g[j] = keep[j];
-        ga.ng = nk;
-        Q = q;
-    }
-    ga.NB = (int)Q;
-    ga.C = a.C, ga.K = K, ga.KD = KD, ga.dg = a.dg;
-    aa.C = a.C, aa.K = K, aa.KD = KD, aa.dg = a.dg;
-    size_t o = 0;
-    pl.o_gcol = o, o = align256(o + (size_t)prow * K * a.C * sizeof(float));
-    // the histogram of one pass, [digit][block] + the digits' totals: (blocks + 1) x 2^db ints with 2^db <= 2 sqrt(anchors),
-    // i.e. at most 4 bytes per sample + 16 sqrt(anchors) -- less than the anchor counters and sample ranks it replaces
-    pl.o_hist = o, o = align256(o + ds_hist_ints(pl.nsamples, pl.nanchors) * sizeof(int));
-    pl.o_start = o, o = align256(o + ((size_t)pl.nanchors + 1) * sizeof(int));
-    pl.o_key = o, o = align256(o + (size_t)pl.nsamples * sizeof(int));
-    pl.o_ent = o, o = align256(o + (size_t)pl.nsamples * sizeof(GEntry));
-    pl.o_gtap = o, o = align256(o + ((size_t)pl.nsamples + 1) * sizeof(Tap));   // + the all-zero entry
-    pl.o_S = o, o = align256(o + (size_t)pl.aa.NA * 4 * a.C * sizeof(float));
-    // corner sums (dcn_offgrad_kernel): one slot per 256-channel block where the per-anchor sums split them over blockIdx.y
-    // (every group on the per-anchor path, C > 256; dcn_gather_kernels.h AnchorArgs::ncb)
-    // (LSN_DBG_ANCHOR_ONE_WAVE: one wave walks all blocks of its anchor, the form until round 6 -- tests; the workspace is sized for
-    // the split either way, so a size asked for under one setting serves a launch under the other)
-    const int ncb_max = (ga.NB == 0 && aa.ng > 0 && a.C > 256) ? cdiv(a.C, 256) : 1;
-    aa.ncb = dbg_on(LSN_DBG_ANCHOR_ONE_WAVE) ? 1 : ncb_max;
-    aa.hb_slot = (long long)pl.nsamples * 4;
-    pl.o_H = o, o = align256(o + (size_t)pl.nsamples * 4 * sizeof(float) * ncb_max);
-    pl.o_pairs = o, o = align256(o + (size_t)pl.nsamples * 2 * sizeof(int2));   // the (key, sample) pairs of the sort, ping and pong
-    pl.bytes = o;
-    pl.ok = true;
-}
-
-// Pixel splits of a weight-gradient launch: the grid (columns x splits x co blocks) fills ONE round of the blocks the chip
-// holds at once (256 CUs x per_cu), rounded DOWN.  Measured on the benchmark step (profiles/r2_wgrad_rounds.txt): the
-// old cdiv(1024, 36) = 29 splits made 1044 blocks = two full rounds plus a third with 20 blocks (0.88 ms per DCN
-// launch); 28 splits 0.68 ms; one round instead of two is the same for the DCN launches and 1.1 ms / step faster over
-// the dense layers (half the fp32 atomics of the epilogues).
-static int wgrad_splits(int cols, int per_cu)
-{
-    const int slots = 256 * per_cu;
-    int s = slots / cols;
-    return s < 1 ? 1 : s;
-}
-
-// weight gradient on the kernels of dcn_mm_kernels.h (it also needs the tap table of the gather pass: route_backward)
-static bool mm_wgrad_ok(const DcnArgs &a) { return mm_common_ok(a) && a.Co % 256 == 0 && (a.C / a.dg) % 64 == 0; }
-// ... and its fragment-order image of grad_output (nchunks 32-pixel chunks) at 32-bit byte offsets
-static bool wgrad_mm_image_ok(const DcnArgs &a, int nchunks) { return fits_i32((int64_t)nchunks * 2 * (a.Co / 32) * mm_npl(), 1024); }
-
-static bool grouped_wgrad_ok(const DcnArgs &a)
-{
-    if (a.groups <= 1 || a.C % a.groups != 0 || a.Co != a.C || a.kh * a.kw > 9) return false;
-    const int cg = a.C / a.groups;
-    if (!(cg == 4 || cg == 8 || cg == 16 || cg == 32) || ((int64_t)a.C * cg) % 256 != 0 || a.C % a.dg != 0) return false;
-    const int nch = cg >= 16 ? cg : 256 / cg;
-    if ((a.C / a.dg) % nch != 0 || a.C % nch != 0) return false;
-    return grouped_inputs_ok(a);
-}
-
-// ---- the route of a call: which kernel serves each pass and what else that fixes.  route_forward / route_backward decide
-// it once, before anything is launched; they are the only callers of the *_ok predicates and of gather_plan, and the three
-// queries of the C ABI (lsn_dcn_backward_workspace_bytes, lsn_dcn_prepared_ok, lsn_dcn_pitched_ok) read their answers. ----
-enum FwdKernel { FWD_MM, FWD_GROUPED, FWD_XN_PLANES, FWD_XN, FWD_FP32 };
-// GATHER_*: column gradients from that kernel, then the atomic-free gather pass; SCATTER_*: fp32 atomics into grad_input
-enum DataKernel { DATA_NONE, GATHER_GROUPED, GATHER_MM, GATHER_XN, SCATTER_XN, SCATTER_FP32 };
-enum WgradKernel { WG_NONE, WG_GROUPED, WG_MM, WG_XN_ORDERED, WG_XN_ATOMIC, WG_FP32_ORDERED, WG_FP32_ATOMIC };
-// what the caller's `workspace` gets: nothing, the fragment-order image of dcn_mm_kernels.h (the only one a caller may
-// hand over prepared), the split bf16 planes (forward) or the split and transposed ones (backward)
-enum WeightImage { IMG_NONE, IMG_FRAGMENT, IMG_PLANES, IMG_PLANES_T };
-
-struct DcnRoute {
-    FwdKernel fwd = FWD_FP32;
-    DataKernel data = DATA_NONE;
-    WgradKernel wgrad = WG_NONE;
-    WeightImage image = IMG_NONE;
-    bool pitched = false;    // out_pitch != Co is served (lsn_dcn_pitched_ok)
-    bool prepared = false;   // weights_prepared is served (lsn_dcn_prepared_ok)
-    int gcol_ks = 0;         // GATHER_GROUPED: k-steps of dcn_gcol_mfma_kernel; 0: the fmaf chains of dcn_gcol_grouped_kernel
-    int wg_steps = 0;        // weight gradient: 32-pixel steps of all levels
-    bool own_gather_ws = false;        // LSN_NCHW without the caller's gather workspace: plan.bytes of the call's own scratch
-    GatherPlan plan;                   // GATHER_*: computed here, once
-    bool gather() const { return data == GATHER_GROUPED || data == GATHER_MM || data == GATHER_XN; }
-};
-
-// Order: mm -> grouped -> xn -> fp32.  The reference-layout (LSN_NCHW) entry points take the same kernels but neither
-// out_pitch nor a prepared image.
-static DcnRoute route_forward(const DcnArgs &a, const lsn_dcn_shape &s, lsn_layout layout)
-{
-    DcnRoute r;
-    const int np = math_np();
-    if (s.workspace && mm_fwd_ok(a)) {
-        r.fwd = FWD_MM, r.image = IMG_FRAGMENT;
-    } else if (grouped_fwd_ok(a)) {
-        r.fwd = FWD_GROUPED;
-    } else if (np != 0 && xn_ok(a) && xn_lds_bytes(split_npl(np), a.kh * a.kw * a.dg) <= 160 * 1024) {
-        r.fwd = FWD_XN;   // with a workspace the weights are split once instead of in every block
-        if (s.workspace && (a.C / a.groups) % 8 == 0) r.fwd = FWD_XN_PLANES, r.image = IMG_PLANES;
-    }
-    r.pitched = r.prepared = layout == LSN_NHWC && r.fwd == FWD_MM;
+    const int K = a.kh * a.kw, KD = K * a.dg;
+    r.C = a.C, r.Co = a.Co, r.kh = a.kh, r.kw = a.kw, r.groups = a.groups, r.dg = a.dg, r.SL = a.SL, r.opitch = a.opitch;
+    r.np = math_np(), r.npl = split_npl(r.np);
+    r.nchw = layout == LSN_NCHW, r.want_wgrad = want_wgrad;
+    r.workspace = s.workspace != nullptr;
+    r.gather_ws = s.gather_workspace != nullptr, r.gather_ws_bytes = gather_ws_bytes(s);
+    // (the rule asks this of the tap table, gather_workspace + plan.o_gtap: o_gtap is a multiple of 256, so it is the same test)
+    r.gather_ws_aligned16 = aligned16(s.gather_workspace);
+    r.general_gemms = dbg_on(LSN_DBG_GENERAL_GEMMS), r.atomic_scatter = dbg_on(LSN_DBG_ATOMIC_SCATTER);
+    r.anchor_one_wave = dbg_on(LSN_DBG_ANCHOR_ONE_WAVE);
+    r.fwd_mm_lds = dcn_fwd_mm_lds_bytes(r.npl, KD), r.xn_lds = xn_lds_bytes(r.npl, KD), r.bwd_xn_lds = bwd_xn_lds_bytes(r.np, KD);
+    r.fwd_grouped_lds = dcn_fwd_grouped_lds_bytes(K);
+    r.wfrag_fwd = cv_wfrag_bytes(a.Co, K, a.C, r.npl), r.wfrag_bwd = cv_wfrag_bytes(K * a.C, 1, a.Co, r.npl);
     return r;
 }
 
-// k-steps of the fp32-MFMA column gradients (dcn_grouped_kernels.h dcn_gcol_mfma_kernel); 0: the fmaf-chain kernel
-static int gcol_mfma_ksteps(const DcnArgs &a)
+// The plan as the kernels take it: prow0 / abase of the levels, and the groups with the pointers of the level that owns each
+static void bind_plan(DcnArgs &a, const GatherPlan &pl, GatherArgs &ga, AnchorArgs &aa)
 {
-    const int Cg = a.C / a.groups, Cog = a.Co / a.groups;
-    if (a.C % GC_COLS != 0 || a.opitch % 4 != 0) return 0;
-    for (int i = 0; i < a.nlv; ++i)
-        if ((reinterpret_cast<uintptr_t>(a.lv[i].gout) & 15) != 0) return 0;
-    if (a.groups == 1) return (a.Co == 64 || a.Co == 128 || a.Co == 256) ? a.Co / 4 : 0;
-    return (Cog == Cg && (Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32)) ? (Cg == 32 ? 8 : 4) : 0;
+    for (int i = 0; i < a.nlv; ++i) a.lv[i].prow0 = pl.prow0[i], a.lv[i].abase = pl.abase[i];
+    const int K = a.kh * a.kw, KD = K * a.dg;
+    ga.ng = pl.nblk, ga.NB = pl.NB, ga.C = a.C, ga.K = K, ga.KD = KD, ga.dg = a.dg;
+    aa.ng = pl.nanc, aa.NA = pl.NA, aa.C = a.C, aa.K = K, aa.KD = KD, aa.dg = a.dg;
+    aa.ncb = pl.ncb, aa.hb_slot = pl.hb_slot;
+    for (int j = 0; j < pl.nblk; ++j) {
+        const GatherPlanGroup &G = pl.blk[j];
+        ga.g[j] = GatherGrp{a.lv[G.level].gx, a.lv[G.level].x, G.B, G.H, G.W, G.abase, G.first};
+    }
+    for (int j = 0; j < pl.nanc; ++j) {
+        const GatherPlanGroup &G = pl.anc[j];
+        aa.g[j] = AnchorGrp{a.lv[G.level].gx, a.lv[G.level].x, G.B, G.H, G.W, G.abase, G.first};
+    }
 }
 
-// grid of the split weight-gradient kernels (dcn_wgrad_kernel / dcn_wgrad_xn_kernel): columns, co blocks; returns the pixel splits
-static int wgrad_split_grid(const DcnArgs &a, int nsteps, int *ncol, int *nz)
+// x / grad_output / grad_input of a channels-last call, as the caller passes them (the callers check what they require)
+static void bind_nhwc(DcnArgs &a, int n, const lsn_dcn_level *lv)
 {
-    const int K = a.kh * a.kw, Cg = a.C / a.groups, Cog = a.Co / a.groups;
-    *ncol = a.groups * K * (Cg / a.SL) * cdiv(a.SL, WG_BN), *nz = cdiv(Cog, WG_BM);
-    int s = wgrad_splits(*ncol * *nz, 2);   // 2 resident blocks per CU (246 VGPRs, 78 KB LDS)
-    if (s > nsteps) s = nsteps;
-    if (s < 1) s = 1;
-    return s > 65535 ? 65535 : s;
-}
-
-// gws / gws_bytes: the caller's gather workspace.  want_wgrad: grad_weight is asked for (the queries answer for that case).
-// Backward-data: the gather path where a column-gradient kernel serves the call -- grouped (groups > 1, or any call of
-// LSN_MATH_FP32), else mm, else xn -- and a gather workspace holds the plan; else scatter xn; else the fp32 scatter.
-// Weight gradient: grouped (dense grad_output, 4 | weight elements) -> mm (reads the gather pass's tap table) -> the split
-// kernels.  A prepared image is served by GATHER_MM (so: groups = 1, a split-bf16 mode, even Co, some data gradient), out_pitch
-// by GATHER_MM and -- when grad_weight is asked for -- WG_MM; neither by the reference-layout (LSN_NCHW) entry points, which
-// get the call's own gather scratch instead of the caller's.
-static DcnRoute route_backward(DcnArgs &a, const lsn_dcn_shape &s, lsn_layout layout, const void *gws, size_t gws_bytes,
-                               bool want_wgrad)
-{
-    DcnRoute r;
-    const int np = math_np(), K = a.kh * a.kw;
-    bool any_data = false;
-    for (int i = 0; i < a.nlv; ++i) any_data = any_data || a.lv[i].gx || a.lv[i].goff || a.lv[i].gmsk;
-    if (any_data) {
-        // can_split: `workspace` gets a bf16 image of the weights (8 bytes per weight element: even Co for the planes)
-        const bool can_split = s.workspace && np && a.groups == 1 && a.Co % 2 == 0;
-        const bool grouped = bwd_grouped_ok(a), mm = mm_bwd_ok(a), x3 = can_split && bwd_x3_ok(a);
-        const DataKernel cand = !bwd_colbuf_env()                         ? DATA_NONE
-                                : grouped                                 ? GATHER_GROUPED
-                                : (can_split && mm && bwd_offsets_ok(a)) ? GATHER_MM
-                                : x3                                      ? GATHER_XN
-                                                                          : DATA_NONE;
-        bool fits = false;
-        if (cand != DATA_NONE && (gws || layout == LSN_NCHW)) {
-            // (all_anchor keys on what the arguments admit, not on the kernel taken: the workspace size a caller asked for
-            // without `workspace` serves the call with it)
-            gather_plan(a, r.plan, mm || grouped);
-            r.own_gather_ws = !gws && r.plan.ok;
-            fits = r.plan.ok && (r.own_gather_ws || r.plan.bytes <= gws_bytes);
-        }
-        r.data = fits ? cand : x3 ? SCATTER_XN : SCATTER_FP32;
-        if (r.data == GATHER_GROUPED) r.gcol_ks = gcol_mfma_ksteps(a);
-        // (the transposed planes are written for every call that can split, also where the fp32 scatter then ignores them)
-        r.image = r.data == GATHER_MM ? IMG_FRAGMENT : can_split ? IMG_PLANES_T : IMG_NONE;
-        r.prepared = layout == LSN_NHWC && r.data == GATHER_MM;
-    }
-    if (want_wgrad) {
-        int64_t rows = 0, steps = 0;
-        for (int i = 0; i < a.nlv; ++i) rows += a.lv[i].P, steps += cdiv(a.lv[i].P, WG_BP);
-        r.wg_steps = (int)steps;
-        const size_t nW = (size_t)a.Co * K * (a.C / a.groups);
-        // the tap table of the gather pass, 16-byte aligned (the call's own scratch is)
-        const bool tap_table = r.gather() && (r.own_gather_ws || ((reinterpret_cast<uintptr_t>(gws) + r.plan.o_gtap) & 15) == 0);
-        if (grouped_wgrad_ok(a) && a.opitch == a.Co && nW % 4 == 0 && rows < ((int64_t)1 << 30)) {
-            r.wgrad = WG_GROUPED;
-        } else if (mm_wgrad_ok(a) && tap_table && wgrad_mm_image_ok(a, r.wg_steps)) {
-            r.wgrad = WG_MM;
-        } else {
-            // one partial gradient per pixel split + an ordered reduce instead of fp32 atomics (deterministic) where they fit
-            int ncol, nz;
-            const int splits = wgrad_split_grid(a, r.wg_steps, &ncol, &nz);
-            const bool ordered = nW % 4 == 0 && (size_t)splits * (nW + a.Co) * sizeof(float) <= ((size_t)256 << 20);
-            r.wgrad = np ? (ordered ? WG_XN_ORDERED : WG_XN_ATOMIC) : (ordered ? WG_FP32_ORDERED : WG_FP32_ATOMIC);
-        }
-    }
-    r.pitched = layout == LSN_NHWC && r.data == GATHER_MM && (!want_wgrad || r.wgrad == WG_MM);
-    return r;
+    for (int i = 0; i < n; ++i) a.lv[i].x = lv[i].input, a.lv[i].gout = lv[i].grad_output, a.lv[i].gx = lv[i].grad_input;
 }
 
 // Tap groups of the split backward-data GEMM (grid.y): the launch runs in ceil(tiles x groups / 512) rounds of the 512
@@ -784,9 +468,12 @@ static int build_lists(DcnArgs &a, const GatherPlan &pl, unsigned char *ws, hipS
     return 0;
 }
 
-static int launch_bwd_gather(DcnArgs &a, DcnRoute &r, unsigned char *ws, hipStream_t st_main)
+static int launch_bwd_gather(DcnArgs &a, const DcnRoute &r, unsigned char *ws, hipStream_t st_main)
 {
-    GatherPlan &pl = r.plan;
+    const GatherPlan &pl = r.plan;
+    GatherArgs ga;
+    AnchorArgs aa;
+    bind_plan(a, pl, ga, aa);
     a.gcol = reinterpret_cast<float *>(ws + pl.o_gcol);
     int *start = reinterpret_cast<int *>(ws + pl.o_start);
     GEntry *ent = reinterpret_cast<GEntry *>(ws + pl.o_ent);
@@ -852,36 +539,36 @@ static int launch_bwd_gather(DcnArgs &a, DcnRoute &r, unsigned char *ws, hipStre
             return rc;
         break;
     }
-    pl.ga.raw = pl.aa.raw = r.data != GATHER_XN ? 1 : 0;
-    pl.ga.Hb = pl.aa.Hb = Hb;
-    pl.ga.gcol = a.gcol, pl.ga.start = start, pl.ga.ent = ent;
-    if (pl.aa.ng > 0) {   // per-anchor sums of all four corners, then four of them per pixel
-        pl.aa.gcol = a.gcol, pl.aa.start = start, pl.aa.ent = ent;
-        pl.aa.S = reinterpret_cast<float *>(ws + pl.o_S);
+    ga.raw = aa.raw = r.data != GATHER_XN ? 1 : 0;
+    ga.Hb = aa.Hb = Hb;
+    ga.gcol = a.gcol, ga.start = start, ga.ent = ent;
+    if (aa.ng > 0) {   // per-anchor sums of all four corners, then four of them per pixel
+        aa.gcol = a.gcol, aa.start = start, aa.ent = ent;
+        aa.S = reinterpret_cast<float *>(ws + pl.o_S);
         if (pl.na_long > 0)
-            hipLaunchKernelGGL(dcn_anchor_sum_kernel<4>, dim3(pl.na_long, pl.aa.ncb), dim3(256), 0, st, pl.aa, 0, pl.na_long);
-        if (pl.aa.NA > pl.na_long)
-            hipLaunchKernelGGL(dcn_anchor_sum_kernel<1>, dim3(cdiv(pl.aa.NA - pl.na_long, 4), pl.aa.ncb), dim3(256), 0, st, pl.aa,
-                               pl.na_long, pl.aa.NA - pl.na_long);
-        hipLaunchKernelGGL(dcn_anchor_combine_kernel, dim3(cdiv(pl.anchor_pixels, 4)), dim3(256), 0, st, pl.aa, pl.anchor_pixels);
+            hipLaunchKernelGGL(dcn_anchor_sum_kernel<4>, dim3(pl.na_long, aa.ncb), dim3(256), 0, st, aa, 0, pl.na_long);
+        if (aa.NA > pl.na_long)
+            hipLaunchKernelGGL(dcn_anchor_sum_kernel<1>, dim3(cdiv(aa.NA - pl.na_long, 4), aa.ncb), dim3(256), 0, st, aa,
+                               pl.na_long, aa.NA - pl.na_long);
+        hipLaunchKernelGGL(dcn_anchor_combine_kernel, dim3(cdiv(pl.anchor_pixels, 4)), dim3(256), 0, st, aa, pl.anchor_pixels);
     }
-    if (pl.ga.NB > 0) {
+    if (ga.NB > 0) {
         // medium lists: four waves per pixel block; short ones (the tower launch, ~140 entries per block): one
-        const bool split = pl.block_samples > (int64_t)300 * pl.ga.NB;
+        const bool split = pl.block_samples > (int64_t)300 * ga.NB;
         if (split)
-            hipLaunchKernelGGL(dcn_gather_kernel<4>, dim3(pl.ga.NB), dim3(256), 0, st, pl.ga);
+            hipLaunchKernelGGL(dcn_gather_kernel<4>, dim3(ga.NB), dim3(256), 0, st, ga);
         else
-            hipLaunchKernelGGL(dcn_gather_kernel<1>, dim3(cdiv(pl.ga.NB, 4)), dim3(256), 0, st, pl.ga);
+            hipLaunchKernelGGL(dcn_gather_kernel<1>, dim3(cdiv(ga.NB, 4)), dim3(256), 0, st, ga);
     }
     if (Hb)
         hipLaunchKernelGGL(dcn_offgrad_kernel, dim3(cdiv(pl.nsamples, 256)), dim3(256), 0, st, a, pl.nsamples,
-                           reinterpret_cast<const float4 *>(Hb), pl.aa.ng > 0 ? pl.aa.ncb : 1);
+                           reinterpret_cast<const float4 *>(Hb), aa.ng > 0 ? aa.ncb : 1);
     LSN_HIP(hipGetLastError());
     return 0;
 }
 
 // gather_ws: the scratch the route's plan was sized for (GATHER_* only)
-static int launch_bwd_data(DcnArgs &a, DcnRoute &r, void *gather_ws, hipStream_t st)
+static int launch_bwd_data(DcnArgs &a, const DcnRoute &r, void *gather_ws, hipStream_t st)
 {
     ProfScope prof(PROF_BWD_DATA, a, st);
     if (r.gather()) return launch_bwd_gather(a, r, reinterpret_cast<unsigned char *>(gather_ws), st);
@@ -893,7 +580,7 @@ static int launch_bwd_data(DcnArgs &a, DcnRoute &r, void *gather_ws, hipStream_t
             constexpr int NP = decltype(npc)::value;
             return launch256(dcn_bwd_data_xn_kernel<NP, false>, dim3(a.ntiles, bwd_tap_groups(a)), bwd_xn_lds_bytes(NP, a.kh * a.kw * a.dg), st, a);
         });
-    return (a.Co / a.groups > 64) ? launch_bwd_data_t<256>(a, st) : launch_bwd_data_t<64>(a, st);
+    return (a.Co / a.groups > 64) ? launch_bwd_data_t<256>(a, r.vec, st) : launch_bwd_data_t<64>(a, r.vec, st);
 }
 
 // 8-byte buffer loads in the split weight-gradient kernel: even channel counts, 8-byte aligned tensors, byte offsets < 2^31
@@ -1012,9 +699,7 @@ static int launch_wgrad_split(const DcnArgs &a_in, const DcnRoute &r, bool accum
     DcnArgs a = a_in;
     a.wg_vec = wgrad_vec_bits(a);
     if ((reinterpret_cast<uintptr_t>(a.gtap) & 15) != 0) a.gtap = nullptr;
-    const int nsteps = r.wg_steps;
-    int ncol, nz;
-    const int splits = wgrad_split_grid(a, nsteps, &ncol, &nz);
+    const int nsteps = r.wg_steps, ncol = r.wg_ncol, nz = r.wg_nz, splits = r.wg_splits;
     const size_t nW = (size_t)a.Co * a.kh * a.kw * (a.C / a.groups);
     const bool ordered = r.wgrad == WG_XN_ORDERED || r.wgrad == WG_FP32_ORDERED;
     if (ordered) {
@@ -1031,7 +716,7 @@ static int launch_wgrad_split(const DcnArgs &a_in, const DcnRoute &r, bool accum
     int rc;
     if (r.wgrad == WG_FP32_ORDERED || r.wgrad == WG_FP32_ATOMIC) {   // exact fp32 (fp32 MFMA)
         const size_t lds = (size_t)WG_BP * (WG_BM + WG_BN) * 4 + 2 * WG_BP * sizeof(Tap);
-        rc = vec_ok(a) ? launch256(dcn_wgrad_kernel<true>, grid, lds, st, a, nsteps) : launch256(dcn_wgrad_kernel<false>, grid, lds, st, a, nsteps);
+        rc = r.vec ? launch256(dcn_wgrad_kernel<true>, grid, lds, st, a, nsteps) : launch256(dcn_wgrad_kernel<false>, grid, lds, st, a, nsteps);
     } else {
         rc = split_dispatch(math_np(), [&](auto np) {
             constexpr int NP = decltype(np)::value;
@@ -1084,7 +769,6 @@ static int prepare_image(DcnArgs &a, WeightImage image, const lsn_dcn_shape &s, 
     return 0;
 }
 
-static size_t gather_ws_bytes(const lsn_dcn_shape &s) { return (size_t)(s.gather_workspace_bytes > 0 ? s.gather_workspace_bytes : 0); }
 static size_t n_in(const lsn_dcn_shape &s, const lsn_dcn_level &d) { return (size_t)d.B * s.C * d.H * d.W; }
 static size_t n_out(const lsn_dcn_shape &s, const lsn_dcn_level &d) { return (size_t)d.B * s.Co * d.Ho * d.Wo; }
 
@@ -1121,7 +805,7 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
         }
     }
     a.bias = bias;
-    const DcnRoute r = route_forward(a, s, layout);
+    const DcnRoute r = route_forward(route_shape(a, s, layout, false));
     if (a.opitch != a.Co && !r.pitched)
         return fail(LSN_ERR_UNSUPPORTED, "deformable forward: out_pitch %d != Co %d outside the matrix-pipe kernels "
                     "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
@@ -1134,7 +818,7 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
     case FWD_GROUPED: rc = launch_forward_grouped(a, st); break;
     case FWD_XN_PLANES: rc = launch_forward_xn(a, true, st); break;
     case FWD_XN: rc = launch_forward_xn(a, false, st); break;
-    case FWD_FP32: rc = launch_forward_fp32(a, st); break;
+    case FWD_FP32: rc = launch_forward_fp32(a, r.vec, st); break;
     }
     if (rc) return rc;
     if (layout == LSN_NCHW)
@@ -1160,11 +844,7 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     if (layout == LSN_NHWC) {
         a.w = weight;
         a.gw = grad_weight;
-        for (int i = 0; i < n; ++i) {
-            a.lv[i].x = lv[i].input;
-            a.lv[i].gout = lv[i].grad_output;
-            a.lv[i].gx = lv[i].grad_input;
-        }
+        bind_nhwc(a, n, lv);
     } else {
         float *w2 = ws.get((size_t)s.Co * Cg * K);
         if (!w2) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
@@ -1192,7 +872,7 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     a.gb = grad_bias;
 
     void *gws = s.gather_workspace;
-    DcnRoute r = route_backward(a, s, layout, gws, gather_ws_bytes(s), a.gw != nullptr);
+    const DcnRoute r = route_backward(route_shape(a, s, layout, a.gw != nullptr));
     if (a.opitch != a.Co && r.data == DATA_NONE)
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward: out_pitch without a data-gradient pass");
     if (a.opitch != a.Co && !r.pitched)
@@ -1267,7 +947,7 @@ static int make_single(lsn_dcn_shape &s, lsn_dcn_level &L, int B, int C, int H, 
 
 // ---- the weight gradient of a dense convolution on this family's kernels (conv.hip validates, routes and accounts the call) ----
 static_assert(CW_MAXLV <= MAXLV && CW_STEP_PX == WG_BP, "conv_wgrad_route.h counts the k-steps of these kernels");
-bool general_gemms_only() { return !dcn_mm_env(); }
+bool general_gemms_only() { return dbg_on(LSN_DBG_GENERAL_GEMMS); }
 
 // The levels of the call as DcnArgs (no offsets: the regular grid is the sampling table); returns the 32-pixel steps
 static int conv_dcn_args(DcnArgs &a, const ConvWgradCall &c)
@@ -1356,48 +1036,42 @@ int lsn_debug_phase_clocks(long long *device_buf_512, int word)
     return 0;
 }
 
-// The queries: the arguments as a channels-last call binds them, then the route such a call would take
-static bool query_args(lsn::DcnArgs &a, const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
+// The queries: the shape of the arguments as a channels-last call binds them, then the route such a call would take
+static bool query_shape(DcnRouteShape &rs, const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward,
+                        bool want_wgrad)
 {
     using namespace lsn;
+    DcnArgs a;
     if (!shape || !levels || check_shape(*shape) != 0) return false;
     if (fill_levels(a, *shape, n_levels, levels, backward ? BWD_BM : 64) != 0) return false;
-    for (int i = 0; i < n_levels; ++i) {
-        a.lv[i].x = levels[i].input;
-        a.lv[i].gout = levels[i].grad_output;
-        a.lv[i].gx = levels[i].grad_input;
-    }
+    bind_nhwc(a, n_levels, levels);
+    rs = route_shape(a, *shape, LSN_NHWC, want_wgrad);
     return true;
 }
 
 int64_t lsn_dcn_backward_workspace_bytes(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels)
 {
-    using namespace lsn;
-    DcnArgs a;
-    if (!query_args(a, shape, n_levels, levels, 1)) return 0;
-    lsn_dcn_shape s = *shape;
-    s.workspace = &s;   // any non-NULL value: the answer is for a call that passes `workspace` and a gather workspace of this size
-    const DcnRoute r = route_backward(a, s, LSN_NHWC, &s, SIZE_MAX, false);
+    DcnRouteShape rs;
+    if (!query_shape(rs, shape, n_levels, levels, 1, false)) return 0;
+    // the answer is for a call that passes `workspace` and a gather workspace of this size
+    rs.workspace = rs.gather_ws = true, rs.gather_ws_bytes = SIZE_MAX;
+    const DcnRoute r = route_backward(rs);
     return r.gather() ? (int64_t)r.plan.bytes : 0;
 }
 
 int lsn_dcn_prepared_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
 {
-    using namespace lsn;
-    DcnArgs a;
-    if (!query_args(a, shape, n_levels, levels, backward)) return 0;
-    if (!backward) return route_forward(a, *shape, LSN_NHWC).prepared ? 1 : 0;
-    return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), false).prepared ? 1 : 0;
+    DcnRouteShape rs;
+    if (!query_shape(rs, shape, n_levels, levels, backward, false)) return 0;
+    return (backward ? route_backward(rs) : route_forward(rs)).prepared ? 1 : 0;
 }
 
 // (backward: the answer is for a call that asks for grad_weight)
 int lsn_dcn_pitched_ok(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels, int backward)
 {
-    using namespace lsn;
-    DcnArgs a;
-    if (!query_args(a, shape, n_levels, levels, backward)) return 0;
-    if (!backward) return route_forward(a, *shape, LSN_NHWC).pitched ? 1 : 0;
-    return route_backward(a, *shape, LSN_NHWC, shape->gather_workspace, gather_ws_bytes(*shape), true).pitched ? 1 : 0;
+    DcnRouteShape rs;
+    if (!query_shape(rs, shape, n_levels, levels, backward, true)) return 0;
+    return (backward ? route_backward(rs) : route_forward(rs)).pitched ? 1 : 0;
 }
 
 // (tests) the anchor lists lsn_dcn_backward would build for this call, and nothing else of it
@@ -1413,20 +1087,18 @@ int lsn_dcn_anchor_lists(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn
     // (the reference-layout entry points route on temporaries of their own, which this entry does not make)
     if (layout != LSN_NHWC) return fail(LSN_ERR_UNSUPPORTED, "lsn_dcn_anchor_lists: LSN_NHWC only");
     if (int rc = fill_levels(a, s, n_levels, levels, BWD_BM)) return rc;
-    for (int i = 0; i < n_levels; ++i) {
-        LSN_CHECK(levels[i].input && levels[i].grad_output, "level %d: input/grad_output is NULL", i);
-        a.lv[i].x = levels[i].input;
-        a.lv[i].gout = levels[i].grad_output;
-        a.lv[i].gx = levels[i].grad_input;
-    }
-    void *gws = s.gather_workspace;
-    DcnRoute r = route_backward(a, s, layout, gws, gather_ws_bytes(s), false);
+    for (int i = 0; i < n_levels; ++i) LSN_CHECK(levels[i].input && levels[i].grad_output, "level %d: input/grad_output is NULL", i);
+    bind_nhwc(a, n_levels, levels);
+    const DcnRoute r = route_backward(route_shape(a, s, layout, false));
     if (!r.gather()) return fail(LSN_ERR_UNSUPPORTED, "lsn_dcn_anchor_lists: this call builds no anchor lists (route without the gather pass)");
     const GatherPlan &pl = r.plan;
     counts[0] = pl.nsamples, counts[1] = pl.nanchors;
     if (!sample_anchor && !list_start && !list_sample) return 0;   // the sizes only
     LSN_CHECK(sample_anchor && list_start && list_sample, "lsn_dcn_anchor_lists: all three outputs or none");
-    unsigned char *w = reinterpret_cast<unsigned char *>(gws);
+    unsigned char *w = reinterpret_cast<unsigned char *>(s.gather_workspace);
+    GatherArgs ga;   // (only the levels' part of the binding is used here)
+    AnchorArgs aa;
+    bind_plan(a, pl, ga, aa);
     if (int rc = build_lists(a, pl, w, st)) return rc;
     const int n = pl.nsamples > pl.nanchors + 1 ? pl.nsamples : pl.nanchors + 1;
     hipLaunchKernelGGL(dcn_list_export_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, pl.nsamples, pl.nanchors,

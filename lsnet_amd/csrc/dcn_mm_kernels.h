@@ -8,7 +8,7 @@
 // It is the dense kernel with ONE phase replaced: the pixel operand of chunk (tap k, 32 channels) is not one float4 per
 // lane but the bilinear blend of four (the sample's corners; corner offsets and mask-weighted corner weights come from a
 // per-workgroup table in LDS that is built once per 64-pixel tile).
-// Conditions (dcn.hip mm_fwd_ok): groups == 1, 32 | C / deformable_groups, 128 | Co; everything else stays on the
+// Conditions (dcn_route.h mm_fwd_ok): groups == 1, 32 | C / deformable_groups, 128 | Co; everything else stays on the
 // kernels of dcn_kernels.h.
 //
 // The backward-data GEMM  gcol[p][k, c] = sum_co gout[p][co] * w[co][k, c]  (deform_conv_cuda.cpp:783-787) needs no
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_mm_kernel(const DcnArgs a, con
 //     corner loads of chunk t + 2 between the MFMAs of chunk t (the schedule of conv_mm_kernel).
 //   * the pixel range is split over blockIdx.y; each split stores its partial tile, conv_wgrad_reduce_kernel adds them in
 //     a fixed order: no atomics, deterministic.
-// Conditions (dcn.hip mm_wgrad_ok): groups == 1, 256 | Co, 64 | C / deformable_groups, the launch-wide sampling table of
+// Conditions (dcn_route.h mm_wgrad_ok): groups == 1, 256 | Co, 64 | C / deformable_groups, the launch-wide sampling table of
 // the backward-data pass (a.gtap).
 // =============================================================================================
 template <int NPL>

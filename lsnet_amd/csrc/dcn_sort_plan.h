@@ -43,7 +43,7 @@ LSN_HD int ds_key_bits(int nanchors)
 }
 LSN_HD int ds_passes(int nanchors) { return ds_key_bits(nanchors) <= 2 * DS_MAX_DIGIT_BITS ? 2 : 3; }
 // digit width of every pass: <= DS_MAX_DIGIT_BITS for every int (a key has at most 31 bits: three passes of 11; the
-// workspace plan of csrc/dcn.hip admits fewer than 2^30 anchors -- three passes of 10 -- and checks the width it gets)
+// workspace plan of csrc/dcn_route.h admits fewer than 2^30 anchors -- three passes of 10 -- and checks the width it gets)
 LSN_HD int ds_digit_bits(int nanchors)
 {
     const int p = ds_passes(nanchors);

@@ -44,7 +44,7 @@ def subsets(leaves):
 
 DCN_LEAVES = ('x', 'off', 'mask', 'w', 'b')
 
-# name -> the request of ONE deformable level that takes the route (csrc/dcn.hip route_backward, ops/hip_backend.py dcn_backward)
+# name -> the request of ONE deformable level that takes the route (csrc/dcn_route.h route_backward, ops/hip_backend.py dcn_backward)
 DCN_ROUTE_REQUESTS = collections.OrderedDict([
     ('weight_without_data', ('w',)),                 # any_data false: DATA_NONE, the weight gradient computes its own taps
     ('weight_bias_without_data', ('w', 'b')),        # the same with the bias sums in the launch

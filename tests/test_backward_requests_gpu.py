@@ -3,7 +3,7 @@ tests/backward_request_cases.py (the deformable family: the CPU oracle).
 
 A. Which gradients are asked for: `requires_grad` flags on the leaves and `.backward()`, as frozen parameters and detached
    inputs do in training.  What is asked for equals the reference at the tolerance the operator's own test uses; every other
-   leaf's .grad stays None.  For the deformable family the request picks the kernels (csrc/dcn.hip route_backward): offsets
+   leaf's .grad stays None.  For the deformable family the request picks the kernels (csrc/dcn_route.h route_backward): offsets
    without their input leave the atomic-free gather for the scatter kernels with a NULL grad_input, no data gradient at all
    leaves the weight gradient without the gather pass's tap table.
 B. Where parameter gradients go: views of one arena registered as gradient sinks (ops/grad_sink.py), prefilled with non-zero

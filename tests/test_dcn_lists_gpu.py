@@ -140,7 +140,7 @@ def expected_anchor(launch, offs, dg=1, stride=1, pad=1, dil=1):
 def _route(launch, groups):
     """The list-building route of the launch.  The library's queries say whether there are lists (a gather workspace size
     above zero) and whether the matrix-pipe GEMM serves the call (lsn_dcn_prepared_ok: GATHER_MM); no query separates the
-    other two, so `groups > 1 or exact-fp32 mode -> GATHER_GROUPED, else GATHER_XN` restates csrc/dcn.hip route_backward here.
+    other two, so `groups > 1 or exact-fp32 mode -> GATHER_GROUPED, else GATHER_XN` restates csrc/dcn_route.h route_backward here.
     A change of the routing rules fails the route assertions of this file for that reason, not because a list is wrong."""
     if launch.ws_bytes <= 0:
         return None

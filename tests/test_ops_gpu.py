@@ -305,7 +305,7 @@ def _kernel_choice(choice):
 @pytest.mark.parametrize('choice', QUERY_CHOICES)
 @pytest.mark.parametrize('case', DCN_CASES, ids=[c['name'] for c in DCN_CASES])
 def test_dcn_queries_match_the_calls(case, choice):
-    """lsn_dcn_prepared_ok / lsn_dcn_pitched_ok and the calls they answer for read one route (csrc/dcn.hip route_forward /
+    """lsn_dcn_prepared_ok / lsn_dcn_pitched_ok and the calls they answer for read one route (csrc/dcn_route.h route_forward /
     route_backward): a call is refused exactly where its query said 0.  The refusals are argument checks in front of every
     launch."""
     with _kernel_choice(choice):
