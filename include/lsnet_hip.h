@@ -143,6 +143,19 @@ int lsn_get_math_mode(void);
 
 /* ---- generic batched entry points (what the Python mirror calls) -------------------------- */
 
+/* Kernel sizes.  kh and kw are free (1x1, 5x5, 1x3, even sizes, ...) as long as KD = kh * kw * deformable_groups <= 64: every
+ * kernel keeps the KD sampling positions of each pixel of its tile in LDS; a larger KD is LSN_ERR_UNSUPPORTED.
+ *   KD <= LSN_DCN_KD_EVERY_ROUTE: every call is served, forward and backward, in every math mode, with or without the
+ *       workspaces, for every channel count.
+ *   LSN_DCN_KD_EVERY_ROUTE < KD <= 64: lsn_dcn_forward serves every call.  lsn_dcn_backward serves the call where a gather route
+ *       takes it (lsn_dcn_backward_workspace_bytes() > 0, that gather_workspace and `workspace` passed) and refuses it with
+ *       LSN_ERR_UNSUPPORTED where only the fp32 atomic-scatter kernel is left, whose tables need 8 KiB + 2816 B * KD of the
+ *       160 KiB of LDS: no gather workspace, channel counts outside the gather routes (C % 4 != 0, ...), the debug bits
+ *       that force the scatter kernels.
+ * A call is served or refused as a whole: every refusal is decided from the arguments in front of the first launch, and a
+ * refused call has written to none of its outputs or workspaces (lsn_last_error() names the LDS need or the bound). */
+#define LSN_DCN_KD_EVERY_ROUTE 55
+
 /* out_l = DCN(input_l, offset_l, mask_l; weight, bias) for l < n_levels.
  * shape->B/H/W/Ho/Wo/scale_* are ignored (taken per level); bias may be NULL. */
 int lsn_dcn_forward(const lsn_dcn_shape *shape, int n_levels, const lsn_dcn_level *levels,

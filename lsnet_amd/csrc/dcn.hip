@@ -108,6 +108,16 @@ struct Scratch {
     }
 };
 
+// The largest kh * kw * deformable_groups that every route of both passes serves (include/lsnet_hip.h LSN_DCN_KD_EVERY_ROUTE).
+// Every kernel keeps the tap table of its 64-pixel tile in LDS, and the route moves on where a kernel's does not fit
+// (dcn_route.h); the fp32 kernels come last, and of their tables the backward's is the larger: 44 bytes per (pixel, tap) beside
+// the 8 KiB weight slab of its 64-wide tile.  Above this count, up to 64, a call is served where its route ends at another
+// kernel and refused -- by the route, in front of every launch -- where it ends at the fp32 scatter.
+constexpr int DCN_KD_EVERY_ROUTE = (int)((DR_LDS_MAX - bwd_fp32_lds(64, 0)) / (bwd_fp32_lds(64, 1) - bwd_fp32_lds(64, 0)));
+static_assert(DCN_KD_EVERY_ROUTE == LSN_DCN_KD_EVERY_ROUTE, "include/lsnet_hip.h states this bound");
+static_assert(bwd_fp32_lds(64, DCN_KD_EVERY_ROUTE) <= DR_LDS_MAX && bwd_fp32_lds(64, DCN_KD_EVERY_ROUTE + 1) > DR_LDS_MAX, "the bound");
+static_assert(fwd_fp32_lds(64, 64) <= DR_LDS_MAX, "the forward pass serves every call check_shape admits");
+
 static int check_shape(const lsn_dcn_shape &s)
 {
     LSN_CHECK(s.kh > 0 && s.kw > 0, "kernel size should be greater than zero, but got kH: %d kW: %d", s.kh, s.kw);
@@ -268,8 +278,9 @@ static int launch_forward_mm(const DcnArgs &a, hipStream_t st)
 template <int BM, int BN, int WM, int WN>
 static int launch_forward_t(const DcnArgs &a, bool vec, hipStream_t st)
 {
+    static_assert(BM == DR_FP32_BM, "dcn_route.h fwd_fp32_lds sizes this tile");
     const int Cog = a.Co / a.groups, KD = a.kh * a.kw * a.dg;
-    const size_t lds = (size_t)(BM + BN) * 33 * 4 + (size_t)BM * KD * sizeof(Tap);
+    const size_t lds = fwd_fp32_lds(BN, KD);   // (<= 160 KiB: route_forward)
     dim3 grid(a.ntiles, cdiv(Cog, BN), a.groups);
     return vec ? launch256(dcn_fwd_kernel<BM, BN, WM, WN, true>, grid, lds, st, a)
                : launch256(dcn_fwd_kernel<BM, BN, WM, WN, false>, grid, lds, st, a);
@@ -290,11 +301,13 @@ static int launch_forward_grouped(const DcnArgs &a_in, hipStream_t st)
     }
 }
 
-// exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU
-static int launch_forward_fp32(const DcnArgs &a, bool vec, hipStream_t st)
+// exact fp32 (LSN_MATH_FP32, narrow outputs, odd channel counts): the fp32-MFMA kernel with two workgroups per CU.
+// bn: the route's tile (DcnRoute::fp32_bn) -- 256 output channels of a group, or 64 where a group has no more or the tap
+// table leaves no room for the wide tile's weight slab
+static int launch_forward_fp32(const DcnArgs &a, int bn, bool vec, hipStream_t st)
 {
     ProfScope prof(PROF_FWD, a, st);
-    return (a.Co / a.groups <= 64) ? launch_forward_t<64, 64, 2, 2>(a, vec, st) : launch_forward_t<64, 256, 1, 4>(a, vec, st);
+    return bn == 64 ? launch_forward_t<64, 64, 2, 2>(a, vec, st) : launch_forward_t<64, 256, 1, 4>(a, vec, st);
 }
 
 // planes: a.wtp holds the weights as dcn_prepare_w_kernel split them; otherwise every block splits its own
@@ -313,7 +326,7 @@ template <int RED>
 static int launch_bwd_data_t(const DcnArgs &a, bool vec, hipStream_t st)
 {
     const int KD = a.kh * a.kw * a.dg;
-    const size_t lds = (size_t)RED * 32 * 4 + (size_t)BWD_BM * KD * (sizeof(Tap) + 12);
+    const size_t lds = bwd_fp32_lds(RED, KD);   // (<= 160 KiB: route_backward)
     return vec ? launch256(dcn_bwd_data_kernel<RED, true>, dim3(a.ntiles), lds, st, a)
                : launch256(dcn_bwd_data_kernel<RED, false>, dim3(a.ntiles), lds, st, a);
 }
@@ -322,6 +335,7 @@ static int launch_bwd_data_t(const DcnArgs &a, bool vec, hipStream_t st)
 static_assert(DR_MAXLV == MAXLV && DR_GT == GT && DR_GF_CH == GF_CH && DR_GC_COLS == GC_COLS, "dcn_route.h plans for these kernels");
 static_assert(DR_WG_BP == WG_BP && DR_WG_BN == WG_BN && DR_WG_BM == WG_BM, "dcn_route.h counts the steps and tiles of these kernels");
 static_assert(DR_TAP_BYTES == sizeof(Tap) && DR_GENTRY_BYTES == sizeof(GEntry), "dcn_route.h sizes the tables of these kernels");
+static_assert(DR_FP32_BM == BWD_BM, "dcn_route.h sizes the tap tables of the fp32 kernels");
 
 static size_t gather_ws_bytes(const lsn_dcn_shape &s) { return (size_t)(s.gather_workspace_bytes > 0 ? s.gather_workspace_bytes : 0); }
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -580,7 +594,7 @@ static int launch_bwd_data(DcnArgs &a, const DcnRoute &r, void *gather_ws, hipSt
             constexpr int NP = decltype(npc)::value;
             return launch256(dcn_bwd_data_xn_kernel<NP, false>, dim3(a.ntiles, bwd_tap_groups(a)), bwd_xn_lds_bytes(NP, a.kh * a.kw * a.dg), st, a);
         });
-    return (a.Co / a.groups > 64) ? launch_bwd_data_t<256>(a, r.vec, st) : launch_bwd_data_t<64>(a, r.vec, st);
+    return r.fp32_red == 256 ? launch_bwd_data_t<256>(a, r.vec, st) : launch_bwd_data_t<64>(a, r.vec, st);
 }
 
 // 8-byte buffer loads in the split weight-gradient kernel: even channel counts, 8-byte aligned tensors, byte offsets < 2^31
@@ -781,7 +795,8 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
     if (int rc = fill_levels(a, s, n, lv, 64)) return rc;
     Scratch ws(st);
     const int K = s.kh * s.kw, Cg = s.C / s.groups;
-    std::vector<float *> out_tmp(n, nullptr);
+    std::vector<float *> out_tmp(n, nullptr), x_tmp(n, nullptr);
+    float *w_tmp = nullptr;
     if (layout == LSN_NHWC) {
         a.w = weight;
         for (int i = 0; i < n; ++i) {
@@ -790,27 +805,36 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
             a.lv[i].out = lv[i].output;
         }
     } else {
-        float *w2 = ws.get((size_t)s.Co * Cg * K);
-        if (!w2) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
-        if (int rc = permute_rs(weight, w2, s.Co, Cg, K, st)) return rc;
-        a.w = w2;
+        // (channels-last temporaries: allocated here, filled behind the route's refusals)
+        w_tmp = ws.get((size_t)s.Co * Cg * K);
+        if (!w_tmp) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
+        a.w = w_tmp;
         for (int i = 0; i < n; ++i) {
             LSN_CHECK(lv[i].input && lv[i].output, "level %d: input/output is NULL", i);
-            float *x2 = ws.get(n_in(s, lv[i]));
+            x_tmp[i] = ws.get(n_in(s, lv[i]));
             out_tmp[i] = ws.get(n_out(s, lv[i]));
-            if (!x2 || !out_tmp[i]) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
-            if (int rc = permute_rs(lv[i].input, x2, lv[i].B, s.C, lv[i].H * lv[i].W, st)) return rc;
-            a.lv[i].x = x2;
+            if (!x_tmp[i] || !out_tmp[i]) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
+            a.lv[i].x = x_tmp[i];
             a.lv[i].out = out_tmp[i];
         }
     }
     a.bias = bias;
+    // the route, and every refusal it implies, in front of the first launch: a refused call has written nothing
     const DcnRoute r = route_forward(route_shape(a, s, layout, false));
+    if (r.lds_over)
+        return fail(LSN_ERR_UNSUPPORTED, "deformable forward: kh*kw*deformable_groups = %d needs %zu B of LDS (> 160 KiB) in the "
+                    "fp32 kernel, the only one left for this call; every call with at most %d is served", K * s.deformable_groups,
+                    r.lds_over, DCN_KD_EVERY_ROUTE);
     if (a.opitch != a.Co && !r.pitched)
         return fail(LSN_ERR_UNSUPPORTED, "deformable forward: out_pitch %d != Co %d outside the matrix-pipe kernels "
                     "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
     if (s.weights_prepared && !r.prepared)
         return fail(LSN_ERR_UNSUPPORTED, "deformable forward: weights_prepared outside the matrix-pipe kernels (lsn_dcn_prepared_ok)");
+    if (layout == LSN_NCHW) {
+        if (int rc = permute_rs(weight, w_tmp, s.Co, Cg, K, st)) return rc;
+        for (int i = 0; i < n; ++i)
+            if (int rc = permute_rs(lv[i].input, x_tmp[i], lv[i].B, s.C, lv[i].H * lv[i].W, st)) return rc;
+    }
     if (int rc = prepare_image(a, r.image, s, false, st)) return rc;
     int rc = 0;
     switch (r.fwd) {
@@ -818,7 +842,7 @@ static int dcn_forward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level *
     case FWD_GROUPED: rc = launch_forward_grouped(a, st); break;
     case FWD_XN_PLANES: rc = launch_forward_xn(a, true, st); break;
     case FWD_XN: rc = launch_forward_xn(a, false, st); break;
-    case FWD_FP32: rc = launch_forward_fp32(a, r.vec, st); break;
+    case FWD_FP32: rc = launch_forward_fp32(a, r.fp32_bn, r.vec, st); break;
     }
     if (rc) return rc;
     if (layout == LSN_NCHW)
@@ -838,30 +862,28 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     if (int rc = fill_levels(a, s, n, lv, BWD_BM)) return rc;
     Scratch ws(st);
     const int K = s.kh * s.kw, Cg = s.C / s.groups;
-    std::vector<float *> gx_tmp(n, nullptr);
-    float *gw_tmp = nullptr;
+    std::vector<float *> gx_tmp(n, nullptr), x_tmp(n, nullptr), go_tmp(n, nullptr);
+    float *gw_tmp = nullptr, *w_tmp = nullptr;
     for (int i = 0; i < n; ++i) LSN_CHECK(lv[i].input && lv[i].grad_output, "level %d: input/grad_output is NULL", i);
     if (layout == LSN_NHWC) {
         a.w = weight;
         a.gw = grad_weight;
         bind_nhwc(a, n, lv);
     } else {
-        float *w2 = ws.get((size_t)s.Co * Cg * K);
-        if (!w2) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
-        if (int rc = permute_rs(weight, w2, s.Co, Cg, K, st)) return rc;
-        a.w = w2;
+        // (channels-last temporaries: allocated here, filled behind the route's refusals)
+        w_tmp = ws.get((size_t)s.Co * Cg * K);
+        if (!w_tmp) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
+        a.w = w_tmp;
         if (grad_weight) {
             gw_tmp = ws.get((size_t)s.Co * Cg * K);
             if (!gw_tmp) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
             a.gw = gw_tmp;
         }
         for (int i = 0; i < n; ++i) {
-            float *x2 = ws.get(n_in(s, lv[i])), *g2 = ws.get(n_out(s, lv[i]));
-            if (!x2 || !g2) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
-            if (int rc = permute_rs(lv[i].input, x2, lv[i].B, s.C, lv[i].H * lv[i].W, st)) return rc;
-            if (int rc = permute_rs(lv[i].grad_output, g2, lv[i].B, s.Co, lv[i].Ho * lv[i].Wo, st)) return rc;
-            a.lv[i].x = x2;
-            a.lv[i].gout = g2;
+            x_tmp[i] = ws.get(n_in(s, lv[i])), go_tmp[i] = ws.get(n_out(s, lv[i]));
+            if (!x_tmp[i] || !go_tmp[i]) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
+            a.lv[i].x = x_tmp[i];
+            a.lv[i].gout = go_tmp[i];
             if (lv[i].grad_input) {
                 gx_tmp[i] = ws.get(n_in(s, lv[i]));
                 if (!gx_tmp[i]) return fail(LSN_ERR_RUNTIME, "workspace allocation failed");
@@ -872,7 +894,12 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
     a.gb = grad_bias;
 
     void *gws = s.gather_workspace;
+    // the route, and every refusal it implies, in front of the first launch: a refused call has written nothing
     const DcnRoute r = route_backward(route_shape(a, s, layout, a.gw != nullptr));
+    if (r.lds_over)
+        return fail(LSN_ERR_UNSUPPORTED, "deformable backward: kh*kw*deformable_groups = %d needs %zu B of LDS (> 160 KiB) in the "
+                    "fp32 scatter kernel, the only one left for this call; every call with at most %d is served",
+                    K * s.deformable_groups, r.lds_over, DCN_KD_EVERY_ROUTE);
     if (a.opitch != a.Co && r.data == DATA_NONE)
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward: out_pitch without a data-gradient pass");
     if (a.opitch != a.Co && !r.pitched)
@@ -880,6 +907,13 @@ static int dcn_backward_impl(const lsn_dcn_shape &s, int n, const lsn_dcn_level 
                     "(lsn_dcn_pitched_ok)", a.opitch, a.Co);
     if (s.weights_prepared && r.data != DATA_NONE && !r.prepared)
         return fail(LSN_ERR_UNSUPPORTED, "deformable backward: weights_prepared outside the matrix-pipe kernels (lsn_dcn_prepared_ok)");
+    if (layout == LSN_NCHW) {
+        if (int rc = permute_rs(weight, w_tmp, s.Co, Cg, K, st)) return rc;
+        for (int i = 0; i < n; ++i) {
+            if (int rc = permute_rs(lv[i].input, x_tmp[i], lv[i].B, s.C, lv[i].H * lv[i].W, st)) return rc;
+            if (int rc = permute_rs(lv[i].grad_output, go_tmp[i], lv[i].B, s.Co, lv[i].Ho * lv[i].Wo, st)) return rc;
+        }
+    }
     if (r.data != DATA_NONE) {
         if (r.own_gather_ws && !(gws = ws.get(r.plan.bytes / 4 + 64)))   // reference-layout entry points: own scratch
             return fail(LSN_ERR_RUNTIME, "workspace allocation failed");

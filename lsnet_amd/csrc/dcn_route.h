@@ -16,6 +16,8 @@ constexpr int DR_GT = 4;                                 // GT: block edge of th
 constexpr int DR_GF_CH = 64, DR_GC_COLS = 64;            // GF_CH, GC_COLS: channels per workgroup of the grouped forward / column gradients
 constexpr int DR_WG_BP = 32, DR_WG_BN = 64, DR_WG_BM = 256;   // WG_BP, WG_BN, WG_BM: tile of the split weight-gradient kernels
 constexpr size_t DR_TAP_BYTES = 32, DR_GENTRY_BYTES = 16;   // sizeof(Tap), sizeof(GEntry)
+constexpr size_t DR_LDS_MAX = 160 * 1024;                 // LDS a workgroup can have (gfx950)
+constexpr int DR_FP32_BM = 64;                            // BWD_BM, and BM of every dcn_fwd_kernel: pixels per workgroup of the fp32 kernels
 
 struct DcnRouteLevel {
     int B, H, W, Ho, Wo;
@@ -94,6 +96,24 @@ inline bool xn_ok(const DcnRouteShape &s)
     for (int i = 0; i < s.n; ++i)
         if (!fits_i32(in_elems(s, i), 4)) return false;
     return true;
+}
+
+// ---- the fp32 kernels of dcn_kernels.h (dcn_fwd_kernel, dcn_bwd_data_kernel): the last kernel of their pass, with the tap table
+// [64 pixels][KD = kh kw dg] of a workgroup in LDS like every kernel in front of them.  Their LDS need is part of the route: a
+// call whose table no tile of theirs leaves room for is refused before anything is launched (DcnRoute::lds_over). ----
+// dcn_fwd_kernel<64, BN>: As[64][33] + Bs[BN][33] floats, tab[64][KD]
+constexpr size_t fwd_fp32_lds(int BN, int KD) { return (size_t)(DR_FP32_BM + BN) * 33 * 4 + (size_t)DR_FP32_BM * KD * DR_TAP_BYTES; }
+// dcn_bwd_data_kernel<RED>: Bs[RED][32] floats, tab[64][KD], gacc[64][KD][3] floats
+constexpr size_t bwd_fp32_lds(int RED, int KD) { return (size_t)RED * 32 * 4 + (size_t)DR_FP32_BM * KD * (DR_TAP_BYTES + 12); }
+// The wide tile (256 output channels of a group per workgroup / per reduction slab) where a group has more than 64 and the
+// table leaves room, else the 64-wide one: more column blocks (forward) or reduction slabs (backward), the same sums.
+inline int fwd_fp32_bn(const DcnRouteShape &s)
+{
+    return s.Co / s.groups > 64 && fwd_fp32_lds(256, s.kh * s.kw * s.dg) <= DR_LDS_MAX ? 256 : 64;
+}
+inline int bwd_fp32_red(const DcnRouteShape &s)
+{
+    return s.Co / s.groups > 64 && bwd_fp32_lds(256, s.kh * s.kw * s.dg) <= DR_LDS_MAX ? 256 : 64;
 }
 
 // ---- grouped calls (dcn_grouped_kernels.h): ResNeXt's 64 groups of 8 / 16 / 32 channels ----
@@ -318,12 +338,15 @@ struct DcnRoute {
     int wg_steps = 0;        // weight gradient: 32-pixel steps of all levels
     int wg_ncol = 0, wg_nz = 0, wg_splits = 0;   // WG_XN_* / WG_FP32_*: grid of the split kernels (columns, co blocks, pixel splits)
     bool own_gather_ws = false;        // LSN_NCHW without the caller's gather workspace: plan.bytes of the call's own scratch
+    int fp32_bn = 0;         // FWD_FP32: output channels per workgroup of dcn_fwd_kernel (256 or 64)
+    int fp32_red = 0;        // SCATTER_FP32: output channels per reduction slab of dcn_bwd_data_kernel (256 or 64)
+    size_t lds_over = 0;     // != 0: no kernel serves the pass -- the LDS bytes (> DR_LDS_MAX) the fp32 kernel would need: the call is refused
     GatherPlan plan;                   // GATHER_*: computed here, once
     bool gather() const { return data == GATHER_GROUPED || data == GATHER_MM || data == GATHER_XN; }
 };
 
-// Order: mm -> grouped -> xn -> fp32.  The reference-layout (LSN_NCHW) entry points take the same kernels but neither
-// out_pitch nor a prepared image.
+// Order: mm -> grouped -> xn -> fp32 (refused where its tap table does not fit: lds_over).  The reference-layout (LSN_NCHW)
+// entry points take the same kernels but neither out_pitch nor a prepared image.
 inline DcnRoute route_forward(const DcnRouteShape &s)
 {
     DcnRoute r;
@@ -335,6 +358,11 @@ inline DcnRoute route_forward(const DcnRouteShape &s)
     } else if (s.np != 0 && xn_ok(s) && s.xn_lds <= 160 * 1024) {
         r.fwd = FWD_XN;   // with a workspace the weights are split once instead of in every block
         if (s.workspace && (s.C / s.groups) % 8 == 0) r.fwd = FWD_XN_PLANES, r.image = IMG_PLANES;
+    }
+    if (r.fwd == FWD_FP32) {
+        r.fp32_bn = fwd_fp32_bn(s);
+        const size_t lds = fwd_fp32_lds(r.fp32_bn, s.kh * s.kw * s.dg);
+        if (lds > DR_LDS_MAX) r.lds_over = lds;
     }
     r.pitched = r.prepared = !s.nchw && r.fwd == FWD_MM;
     return r;
@@ -363,7 +391,8 @@ inline int wgrad_split_grid(const DcnRouteShape &s, int nsteps, int *ncol, int *
 }
 
 // Backward-data: the gather path where a column-gradient kernel serves the call -- grouped (groups > 1, or any call of
-// LSN_MATH_FP32), else mm, else xn -- and a gather workspace holds the plan; else scatter xn; else the fp32 scatter.
+// LSN_MATH_FP32), else mm, else xn -- and a gather workspace holds the plan; else scatter xn; else the fp32 scatter (refused
+// where its tap table does not fit: lds_over).
 // Weight gradient: grouped (dense grad_output, 4 | weight elements) -> mm (reads the gather pass's tap table) -> the split
 // kernels.  A prepared image is served by GATHER_MM (so: groups = 1, a split-bf16 mode, even Co, some data gradient), out_pitch
 // by GATHER_MM and -- when grad_weight is asked for -- WG_MM; neither by the reference-layout (LSN_NCHW) entry points, which
@@ -394,6 +423,11 @@ inline DcnRoute route_backward(const DcnRouteShape &s)
         }
         r.data = fits ? cand : x3 ? SCATTER_XN : SCATTER_FP32;
         if (r.data == GATHER_GROUPED) r.gcol_ks = gcol_mfma_ksteps(s);
+        if (r.data == SCATTER_FP32) {
+            r.fp32_red = bwd_fp32_red(s);
+            const size_t lds = bwd_fp32_lds(r.fp32_red, K * s.dg);
+            if (lds > DR_LDS_MAX) r.lds_over = lds;
+        }
         // (the transposed planes are written for every call that can split, also where the fp32 scatter then ignores them)
         r.image = r.data == GATHER_MM ? IMG_FRAGMENT : can_split ? IMG_PLANES_T : IMG_NONE;
         r.prepared = !s.nchw && r.data == GATHER_MM;

@@ -33,16 +33,16 @@ def _case(name):
 
 class Launch:
     """One channels-last lsn_dcn_backward launch at the C ABI, built as HipBackend._dcn_backward_call builds it.  levels: dicts
-    with x (B, C, H, W), off (B, dg 18, Ho, Wo), optional mask, optional scale (sh, sw), want_gx (default True).  Levels whose
-    x is the same tensor share one grad_input buffer."""
+    with x (B, C, H, W), off (B, dg 2 kh kw, Ho, Wo), optional mask, optional scale (sh, sw), want_gx (default True).  Levels whose
+    x is the same tensor share one grad_input buffer.  k: the kernel (kh, kw)."""
 
-    def __init__(self, levels, Co, groups=1, dg=1, stride=1, pad=1, dil=1):
+    def __init__(self, levels, Co, groups=1, dg=1, stride=1, pad=1, dil=1, k=(3, 3)):
         from lsnet_amd.ops.hip_backend import HipBackend, _strides
         self.lib = _lib.load()
         dev = _dev()
         self.keep = []
         C = levels[0]['x'].shape[1]
-        w = torch.zeros(Co, C // groups, 3, 3, device=dev).contiguous(memory_format=_CL)
+        w = torch.zeros(Co, C // groups, k[0], k[1], device=dev).contiguous(memory_format=_CL)
         self.shape = HipBackend._shape(w, dict(stride=stride, pad=pad, dil=dil, groups=groups, dg=dg))
         self.n = len(levels)
         self.levels = (_lib.DcnLevel * self.n)()
@@ -115,18 +115,20 @@ def check_lists(anchor, start, sample, na):
     return listed
 
 
-def expected_anchor(launch, offs, dg=1, stride=1, pad=1, dil=1):
-    """Keys from the sampling arithmetic: sample (pixel, group, tap) of level l at py = fl(fl((ho s - p + i d) sh) + dy); its
-    anchor is (floor(py) + 1, floor(px) + 1) on the (B, H + 1, W + 1) grid of its grad_input buffer.  One buffer per level
-    here (the shared-buffer launches state their anchors themselves)."""
+def expected_anchor(launch, offs, dg=1, stride=1, pad=1, dil=1, k=(3, 3)):
+    """Keys from the sampling arithmetic: sample (pixel, group, tap) of level l at py = fl(fl((ho s - p + i d) sh) + dy), tap
+    (i, j) = divmod(tap, kw) of the kernel k = (kh, kw); its anchor is (floor(py) + 1, floor(px) + 1) on the (B, H + 1, W + 1) grid
+    of its grad_input buffer.  One buffer per level here (the shared-buffer launches state their anchors themselves)."""
     out, abase = [], 0
+    kh, kw = k
+    K = kh * kw
     for (B, H, W, Ho, Wo), off, L in zip(launch.geom, offs, launch.levels):
-        off = off.to(_dev()).float().view(B, dg, 9, 2, Ho, Wo)
-        k = torch.arange(9, device=off.device)
+        off = off.to(_dev()).float().view(B, dg, K, 2, Ho, Wo)
+        k = torch.arange(K, device=off.device)
         ho = torch.arange(Ho, device=off.device).view(1, 1, 1, Ho, 1)
         wo = torch.arange(Wo, device=off.device).view(1, 1, 1, 1, Wo)
-        by = (ho * stride - pad + (k // 3).view(1, 1, 9, 1, 1) * dil).float() * torch.tensor(L.scale_h, dtype=torch.float32)
-        bx = (wo * stride - pad + (k % 3).view(1, 1, 9, 1, 1) * dil).float() * torch.tensor(L.scale_w, dtype=torch.float32)
+        by = (ho * stride - pad + (k // kw).view(1, 1, K, 1, 1) * dil).float() * torch.tensor(L.scale_h, dtype=torch.float32)
+        bx = (wo * stride - pad + (k % kw).view(1, 1, K, 1, 1) * dil).float() * torch.tensor(L.scale_w, dtype=torch.float32)
         py, px = by + off[:, :, :, 0], bx + off[:, :, :, 1]
         inside = (py > -1) & (px > -1) & (py < H) & (px < W)
         b = torch.arange(B, device=off.device).view(B, 1, 1, 1, 1)

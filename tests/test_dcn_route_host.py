@@ -22,7 +22,7 @@ def test_route_table_under_sanitizers(tmp_path):
     print(run.stdout)
     assert run.returncode == 0, run.stdout
     lines = [ln for ln in run.stdout.splitlines() if ln.strip()]
-    assert len(lines) == 69 and all(ln.endswith(' ok') for ln in lines), run.stdout
+    assert len(lines) == 86 and all(ln.endswith(' ok') for ln in lines), run.stdout
     # every value of the four enums is reached: "<name>: <fwd>/<image> <data>/<image> <wgrad> ok"
     routes = [ln.rsplit(': ', 1)[1].split() for ln in lines[:-1]]
     assert {r[0].split('/')[0] for r in routes} == set(FWD)
@@ -40,3 +40,16 @@ def test_route_table_under_sanitizers(tmp_path):
                 'wgrad 3x3 64->256 gather workspace at offset 4: FWD_MM/IMG_FRAGMENT GATHER_MM/IMG_FRAGMENT WG_XN_ORDERED ok',
                 'plan direct 8x8 <- 8192x16384 (9 x 2^27 samples): refused ok'):
         assert row in lines, row
+    # every LDS threshold is cut in kh kw dg on both sides, and the grouped weight gradient at nine and ten taps
+    for row in ('kd 28 = 2x7 dg 2, 64->128 (fwd_mm_lds 81920 = the cap): FWD_MM/IMG_FRAGMENT GATHER_MM/IMG_FRAGMENT WG_NONE ok',
+                'kd 29 = 1x29, 64->128 (fwd_mm_lds 83968): FWD_FP32/IMG_NONE GATHER_MM/IMG_FRAGMENT WG_NONE ok',
+                'kd 20 = 2x5 dg 2, 64->192 (xn_lds 163840 = the cap): FWD_XN_PLANES/IMG_PLANES GATHER_MM/IMG_FRAGMENT WG_NONE ok',
+                'kd 21 = 1x21, 64->192 (xn_lds 165888): FWD_FP32/IMG_NONE GATHER_MM/IMG_FRAGMENT WG_NONE ok',
+                'kd 11 = 1x11, 64->128 no gather workspace (bwd_xn_lds 80128): FWD_MM/IMG_FRAGMENT SCATTER_XN/IMG_PLANES_T WG_NONE ok',
+                'kd 12 = 2x3 dg 2, 64->128 no gather workspace (bwd_xn_lds 82944): FWD_MM/IMG_FRAGMENT SCATTER_FP32/IMG_PLANES_T WG_NONE ok',
+                'wgrad 1x9 512->512 64 groups (9 taps): FWD_GROUPED/IMG_NONE GATHER_GROUPED/IMG_NONE WG_GROUPED ok',
+                'wgrad 2x5 512->512 64 groups (10 taps): FWD_GROUPED/IMG_NONE GATHER_GROUPED/IMG_NONE WG_XN_ORDERED ok'):
+        assert row in lines, row
+    # the refusal of the fp32 scatter is part of the route: the last count every route serves, and the first one it refuses
+    assert sum('(bwd_fp32_lds 64-wide 163072: the last count every route serves)' in ln for ln in lines) == 1
+    assert sum('(bwd_fp32_lds 64-wide 165888: refused)' in ln for ln in lines) == 1

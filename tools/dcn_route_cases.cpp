@@ -10,7 +10,9 @@
 // replaced (csrc/dcn.hip's route_forward / route_backward / gather_plan of the commit before it), called through the C ABI's
 // argument filling for the same call; so were the numbers of kernels(): what the kernels' own functions give for the row's taps,
 // channels and math mode (dcn_fwd_mm_lds_bytes, xn_lds_bytes, bwd_xn_lds_bytes, dcn_fwd_grouped_lds_bytes, cv_wfrag_bytes
-// forward and backward).  Rows at a cap take the shape whose real numbers lie on either side of it.
+// forward and backward).  Rows at a cap take the shape whose real numbers lie on either side of it.  The rows "kd N" cut each LDS
+// threshold in KD = kh kw dg at the largest count the kernel keeps and at the next one; their numbers follow from the formulas
+// quoted above each pair, and their texts also state the fp32 kernels' part of the route (" | fp32 bn red over=fwd/bwd").
 // Unless a case says otherwise: six products per product, one level of 2 x 13 x 17 pixels that wants all three data gradients,
 // both workspaces (the gather workspace large enough), aligned pointers, the debug bits clear, channels-last, no grad_weight.
 //
@@ -108,11 +110,20 @@ static std::string text(const DcnRouteShape &s, const DcnRoute &f, const DcnRout
     return o;
 }
 
+// the fp32 kernels' part of both routes: the forward tile, the backward reduction slab, the LDS bytes of a refusal (0: served)
+static std::string fp32_text(const DcnRoute &f, const DcnRoute &r)
+{
+    char b[128];
+    snprintf(b, sizeof b, " | fp32 bn=%d red=%d over=%zu/%zu", f.fp32_bn, r.fp32_red, f.lds_over, r.lds_over);
+    return b;
+}
+
 static int g_bad = 0;
-static void expect(const char *name, const DcnRouteShape &s, const char *want)
+// fp32: the row also states fp32_text (the rows of the KD thresholds; the others predate those fields and keep their texts)
+static void expect(const char *name, const DcnRouteShape &s, const char *want, bool fp32 = false)
 {
     const DcnRoute f = route_forward(s), r = route_backward(s);
-    const std::string got = text(s, f, r);
+    const std::string got = text(s, f, r) + (fp32 ? fp32_text(f, r) : std::string());
     printf("%s: %s/%s %s/%s %s", name, FWD[f.fwd], IMG[f.image], DATA[r.data], IMG[r.image], WG[r.wgrad]);
     if (got == want) {
         printf(" ok\n");
@@ -435,6 +446,90 @@ int main()
     s.want_wgrad = true;
     expect("wgrad 3x3 256->256 tower 2x100x168", s,
            "fwd=0 image=1 pitched=1 prepared=1 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=2 wg_steps=1050 grid=0/0/0 | plan ok=1 ns=302400 na=34138 o=0,309657600,309810176,309946880,311156480,315994880,325671936,465501184,470339584 bytes=475177984 NB=0 NA=34138 na_long=0 ncb=1 hb_slot=1209600 apx=33600 bs=0 lv 0:0 blk anc 0:2,100,168,0,0");
+    // ---- the LDS thresholds cut in KD = kh kw dg, the largest count a kernel keeps and the next one (six products: npl = 3) ----
+    // fwd_mm_lds = 8192 npl + 2048 KD <= 80 KiB: KD <= 28
+    s = shape(64, 128, 2, 7, 1, 2, {L0});
+    kernels(s, 6, 3, 81920, 180224, 128000, 31744, 688128, 688128);
+    expect("kd 28 = 2x7 dg 2, 64->128 (fwd_mm_lds 81920 = the cap)", s,
+           "fwd=0 image=1 pitched=1 prepared=1 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=12376 na=504 o=0,1584128,1585152,1587200,1636864,1835008,2231296,2747392,2945536 bytes=3143680 NB=0 NA=504 na_long=0 ncb=1 hb_slot=49504 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=0 red=0 over=0/0", true);
+    s = shape(64, 128, 1, 29, 1, 1, {L0});
+    kernels(s, 6, 3, 83968, 182272, 130816, 47104, 1425408, 1474560);
+    expect("kd 29 = 1x29, 64->128 (fwd_mm_lds 83968)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=12818 na=504 o=0,3281408,3282432,3284480,3335936,3541248,3951616,4467712,4673024 bytes=4878336 NB=0 NA=504 na_long=0 ncb=1 hb_slot=51272 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=256 red=0 over=0/0", true);
+    // xn_lds = 40960 npl + 2048 KD <= 160 KiB: KD <= 20
+    s = shape(64, 192, 2, 5, 1, 2, {L0});
+    kernels(s, 6, 3, 65536, 163840, 105472, 27648, 983040, 737280);
+    expect("kd 20 = 2x5 dg 2, 64->192 (xn_lds 163840 = the cap)", s,
+           "fwd=2 image=2 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=8840 na=504 o=0,1131520,1132288,1134336,1169920,1311488,1594624,2110720,2252288 bytes=2393856 NB=0 NA=504 na_long=0 ncb=1 hb_slot=35360 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=0 red=0 over=0/0", true);
+    s = shape(64, 192, 1, 21, 1, 1, {L0});
+    kernels(s, 6, 3, 67584, 165888, 108288, 38912, 2064384, 1622016);
+    expect("kd 21 = 1x21, 64->192 (xn_lds 165888)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=9282 na=504 o=0,2376192,2376960,2379008,2416384,2565120,2862336,3378432,3527168 bytes=3675904 NB=0 NA=504 na_long=0 ncb=1 hb_slot=37128 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=256 red=0 over=0/0", true);
+    // bwd_xn_lds = 16384 npl + 2816 KD <= 80 KiB: KD <= 11
+    s = shape(64, 128, 1, 11, 1, 1, {L0});
+    kernels(s, 6, 3, 47104, 145408, 80128, 28672, 540672, 589824);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 11 = 1x11, 64->128 no gather workspace (bwd_xn_lds 80128)", s,
+           "fwd=0 image=1 pitched=1 prepared=1 vec=1 | data=4 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=0 red=0 over=0/0", true);
+    s = shape(64, 128, 2, 3, 1, 2, {L0});
+    kernels(s, 6, 3, 49152, 147456, 82944, 23552, 294912, 294912);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 12 = 2x3 dg 2, 64->128 no gather workspace (bwd_xn_lds 82944)", s,
+           "fwd=0 image=1 pitched=1 prepared=1 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=0 red=256 over=0/0", true);
+    // grouped weight gradient: kh kw <= 9
+    s = shape(512, 512, 1, 9, 64, 1, {L0});
+    kernels(s, 6, 3, 43008, 141312, 74496, 26624, 14155776, 14155776);
+    s.want_wgrad = true;
+    expect("wgrad 1x9 512->512 64 groups (9 taps)", s,
+           "fwd=1 image=0 pitched=0 prepared=0 vec=1 | data=1 image=0 prepared=0 pitched=0 gcol_ks=4 own=0 wgrad=1 wg_steps=14 grid=0/0/0 | plan ok=1 ns=3978 na=504 o=0,8146944,8147456,8149504,8165632,8229376,8356864,12485632,12613120 bytes=12676864 NB=0 NA=504 na_long=0 ncb=2 hb_slot=15912 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=0 red=0 over=0/0", true);
+    s = shape(512, 512, 2, 5, 64, 1, {L0});
+    kernels(s, 6, 3, 45056, 143360, 77312, 27648, 15728640, 15728640);
+    s.want_wgrad = true;
+    expect("wgrad 2x5 512->512 64 groups (10 taps)", s,
+           "fwd=1 image=0 pitched=0 prepared=0 vec=1 | data=1 image=0 prepared=0 pitched=0 gcol_ks=4 own=0 wgrad=3 wg_steps=14 grid=640/1/1 | plan ok=1 ns=4420 na=504 o=0,9052160,9052672,9054720,9072640,9143552,9285120,13413888,13555456 bytes=13626368 NB=0 NA=504 na_long=0 ncb=2 hb_slot=17680 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=0 red=0 over=0/0", true);
+    // ---- the fp32 kernels, last of their pass: the 256-wide tile while the tap table leaves room for it, then the 64-wide one,
+    // then -- backward only, kh kw dg <= 64 -- the refusal.  fwd_fp32_lds = 33 x 4 (64 + BN) + 2048 KD, bwd_fp32_lds = 128 RED + 2816 KD ----
+    s = shape(64, 192, 1, 59, 1, 1, {L0});
+    kernels(s, 6, 3, 145408, 243712, 215296, 77824, 5799936, 4423680);
+    expect("kd 59 = 1x59, 64->192 (fwd_fp32_lds 256-wide 163072)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=26078 na=504 o=0,6675968,6677760,6679808,6784256,7201536,8036096,8552192,8969472 bytes=9386752 NB=0 NA=504 na_long=504 ncb=1 hb_slot=104312 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=256 red=0 over=0/0", true);
+    s = shape(64, 192, 6, 10, 1, 1, {L0});
+    kernels(s, 6, 3, 147456, 245760, 218112, 78848, 5898240, 4423680);
+    expect("kd 60 = 6x10, 64->192 (fwd_fp32_lds 256-wide 165120, 64-wide 139776)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=26520 na=504 o=0,6789120,6790912,6792960,6899200,7323648,8172544,8688640,9113088 bytes=9537536 NB=0 NA=504 na_long=504 ncb=1 hb_slot=106080 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=64 red=0 over=0/0", true);
+    s = shape(64, 128, 2, 23, 1, 1, {L0});
+    kernels(s, 6, 3, 118784, 217088, 178688, 64512, 2260992, 2260992);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 46 = 2x23, 64->128 no gather workspace (bwd_fp32_lds 256-wide 162304)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=256 red=256 over=0/0", true);
+    s = shape(64, 128, 1, 47, 1, 1, {L0});
+    kernels(s, 6, 3, 120832, 219136, 181504, 65536, 2310144, 2359296);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 47 = 1x47, 64->128 no gather workspace (bwd_fp32_lds 256-wide 165120, 64-wide 140544)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=256 red=64 over=0/0", true);
+    s = shape(64, 128, 5, 11, 1, 1, {L0});
+    kernels(s, 6, 3, 137216, 235520, 204032, 73728, 2703360, 2752512);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 55 = 5x11, 64->128 no gather workspace (bwd_fp32_lds 64-wide 163072: the last count every route serves)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=256 red=64 over=0/0", true);
+    s = shape(64, 128, 7, 8, 1, 1, {L0});
+    kernels(s, 6, 3, 139264, 237568, 206848, 74752, 2752512, 2752512);
+    s.gather_ws = false, s.gather_ws_bytes = 0;
+    expect("kd 56 = 7x8, 64->128 no gather workspace (bwd_fp32_lds 64-wide 165888: refused)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=256 red=64 over=0/165888", true);
+    s = shape(64, 128, 7, 8, 1, 1, {L0});
+    kernels(s, 6, 3, 139264, 237568, 206848, 74752, 2752512, 2752512);
+    expect("kd 56 = 7x8, 64->128 (the gather route serves it)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=2 image=1 prepared=1 pitched=1 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=24752 na=504 o=0,6336512,6338304,6340352,6439424,6835456,7627776,8143872,8539904 bytes=8935936 NB=0 NA=504 na_long=504 ncb=1 hb_slot=99008 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=256 red=0 over=0/0", true);
+    s = shape(32, 32, 8, 8, 1, 1, {L0});
+    kernels(s, 6, 3, 155648, 253952, 229376, 82944, 393216, 393216);
+    s.atomic_scatter = true;
+    expect("kd 64 = 8x8, 32->32 atomic-scatter bit (fwd_fp32_lds 64-wide 147968; bwd_fp32_lds 188416: refused)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=5 image=3 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=0 | fp32 bn=64 red=64 over=0/188416", true);
+    s = shape(32, 32, 8, 8, 1, 1, {L0});
+    kernels(s, 0, 0, 131072, 131072, 180224, 82944, 0, 0);
+    expect("kd 64 = 8x8, 32->32 exact mode (the grouped gather serves it)", s,
+           "fwd=4 image=0 pitched=0 prepared=0 vec=1 | data=1 image=0 prepared=0 pitched=0 gcol_ks=0 own=0 wgrad=0 wg_steps=0 grid=0/0/0 | plan ok=1 ns=28288 na=504 o=0,3620864,3622912,3624960,3738112,4190720,5096192,5354240,5806848 bytes=6259456 NB=0 NA=504 na_long=504 ncb=1 hb_slot=113152 apx=442 bs=0 lv 0:0 blk anc 0:2,13,17,0,0 | fp32 bn=64 red=0 over=0/0", true);
     // ---- gather_plan directly: 2^27 pixel rows of nine samples are 9 x 2^27 >= 2^30 samples (no route reaches the plan with them) ----
     s = shape(64, 128, 3, 3, 1, 1, {{1, 8, 8, 8192, 16384, 0, true, true}});
     kernels(s, 6, 3, 43008, 141312, 74496, 26624, 442368, 491520);
