@@ -389,6 +389,45 @@ int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const in
 int lsn_dense_targets(const int64_t *gt_inds, int P, const float *table /* (G, D) */, int D, float *out /* (P, D) */,
                       lsn_stream_t stream);
 
+/* ---- ragged batches: images smaller than the padded batch ---------------------------------------
+ * valid: (B, P) / (B, N) bytes on the device or NULL, the convention of lsn_corner_targets_batch: non-zero = the point / box
+ * exists for image b (the `inside` flags of lsnet_head.py:810-816).  With valid == NULL the two _masked_batch calls ARE
+ * lsn_centroid_assign_batch / lsn_atss_assign_batch: the same kernels, the same bits.  Workspace as for those (the mask
+ * needs none), three launches, asynchronous, no allocation, no host read, independent of workgroup order.
+ *
+ * A row that does not exist for an image is never a candidate of that image's gts and comes out as background: gt_inds 0,
+ * labels -1, max_overlaps -1e8.  The result equals the single-image call on the filtered rows, scattered back (row order,
+ * and with it every tie rule, is kept), under one condition each:
+ *   Centroid: a gt's level is clamped to the levels present among ALL P points.  That is the reference's range over the
+ *     filtered points only while every level keeps at least one valid point in every image.  A level short of pos_num valid
+ *     points gives fewer ("fewer when the level has fewer points" above).
+ *   ATSS: level_len stays the full length (each >= topk).  A level with fewer than topk valid rows for some image simply
+ *     yields a shorter candidate list, as NaN distances do; torch.topk's error on the filtered level is NOT reproduced.
+ *     A caller that wants that error compares its host-side counts of valid rows with topk before the call. */
+int lsn_centroid_assign_masked_batch(const float *points, int P, const uint8_t *valid /* (B,P) or NULL */,
+                                     const float *gt_bboxes, const float *centres, int B, const int *gt_offset, float scale,
+                                     int pos_num, const int64_t *gt_labels, int64_t *gt_inds, int64_t *labels,
+                                     void *workspace, lsn_stream_t stream);
+int lsn_atss_assign_masked_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len,
+                                 const uint8_t *valid /* (B,N) or NULL */, const float *gt_bboxes, int B,
+                                 const int *gt_offset, int topk, const int64_t *gt_labels, int64_t *gt_inds,
+                                 float *max_overlaps, int64_t *labels, void *workspace, lsn_stream_t stream);
+/* The per-point targets of a stage for all B <= 64 images, one launch: what LSHead's per-image gather (lsn_dense_targets and
+ * the label / weight statements, lsnet_head.py:834-890) followed by the scatter into the full grid (unmap, :893-917) leaves.
+ * gt_inds (B, P): an assignment of the image's gts (gt_offset as above; values outside 1 .. G_b count as background);
+ * table (G_total, D): boxes first, then extreme points / polygons / keypoints and visibilities side by side (NULL only when
+ * there is no gt); gt_labels (G_total) or NULL.  A point is positive when it is valid and assigned.
+ *   rows (B, P, D)         the assigned gt's table row, zeros otherwise
+ *   labels (B, P)          positive: gt_labels[...] (1 when gt_labels is NULL); valid, not positive: background_label; else 0
+ *   label_weights (B, P)   1 valid, 0 not
+ *   bbox_weights (B, P, 4) 1 positive, else 0 (16-byte aligned)
+ *   num_pos (B)            positives of image b: an integer sum, no atomic
+ * Asynchronous, no workspace, no allocation, no host read. */
+int lsn_assign_targets_batch(const int64_t *gt_inds, const uint8_t *valid /* (B,P) or NULL */, int P, int B,
+                             const int *gt_offset, const float *table, int D, const int64_t *gt_labels,
+                             int64_t background_label, float *rows, int64_t *labels, float *label_weights,
+                             float *bbox_weights, int64_t *num_pos, lsn_stream_t stream);
+
 /* ---- NMS: nms_ext.cpp:18-29 ---------------------------------------------------------------- */
 /* dets (n,5) = x1,y1,x2,y2,score on the device.  keep (capacity n, int64, device) receives the
  * kept indices into the INPUT order, in descending score order; *num_keep (device int64) their

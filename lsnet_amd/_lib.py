@@ -182,6 +182,9 @@ def _signatures():
         'lsn_atss_assign': (i, [p, i, i, i, p, p, i, i] + [p] * 6),
         'lsn_atss_assign_batch': (i, [p, i, i, i, p, p, i, p, i] + [p] * 6),
         'lsn_dense_targets': (i, [p, i, p, i, p, p]),
+        'lsn_centroid_assign_masked_batch': (i, [p, i, p, p, p, i, p, f, i] + [p] * 5),
+        'lsn_atss_assign_masked_batch': (i, [p, i, i, i, p, p, p, i, p, i] + [p] * 6),
+        'lsn_assign_targets_batch': (i, [p, p, i, i, p, p, i, p, q] + [p] * 6),
         'lsn_nms_workspace_bytes': (q, [i]),
         'lsn_nms': (i, [p, p, i, f] + [p] * 4),
         'lsn_conv2d_prepared_bytes': (q, [i] * 8),

@@ -9,7 +9,8 @@ contract), written with `where`/`scatter` instead of masked assignment so that n
 host-side shapes.
 
 On the device the two assigners run as kernels of the library (`lsn_centroid_assign`, `lsn_atss_assign`: csrc/assign.hip,
-arithmetic in csrc/assign_rows.h) -- same integers, no (points x gts) matrix.  The torch statements below stay as they
+arithmetic in csrc/assign_rows.h) -- same integers, no (points x gts) matrix; `assign_batch(valid=...)` assigns a ragged batch
+(images smaller than the padded batch) in one masked call, the filtered images' integers.  The torch statements below stay as they
 are: the checker of those kernels and the path of host tensors, other dtypes, levels shorter than `topk` and
 LSNET_NATIVE_ASSIGN=0."""
 import os
@@ -23,6 +24,9 @@ BBOX_SAMPLERS = Registry('bbox_sampler')
 IOU_CALCULATORS = Registry('IoU calculator')
 # LSNET_NATIVE_ASSIGN=0: the torch statements on the device too (A/B switch; the tests compare the two)
 NATIVE_ASSIGN = os.environ.get('LSNET_NATIVE_ASSIGN', '1') != '0'
+# LSNET_NATIVE_RAGGED=0: a batch with an image smaller than the padded batch is assigned image by image on its filtered
+# points (boolean indexing: host synchronisations) instead of by one masked call per stage (LSHead.get_targets)
+NATIVE_RAGGED = os.environ.get('LSNET_NATIVE_RAGGED', '1') != '0'
 
 
 def _native(*tensors):
@@ -160,13 +164,15 @@ class CentroidAssigner:
         gt_inds = torch.where(best_d != INF, best_gt + 1, 0)
         return AssignResult(num_gts, gt_inds, None, labels=_labels_of(gt_inds, gt_labels))
 
-    def assign_batch(self, points, gt_bboxes, gt_extreme_pts, gt_labels=None):
+    def assign_batch(self, points, gt_bboxes, gt_extreme_pts, gt_labels=None, valid=None):
         """All images of a batch over the SAME points in one call of the library: gt_bboxes / gt_extreme_pts / gt_labels are
-        per-image lists (an image may have no gt).  -> list of AssignResult, or None when the kernels do not take the
-        inputs (the caller then assigns image by image)."""
+        per-image lists (an image may have no gt).  valid: (B, P) bool / uint8 on the device or None -- the points that lie
+        inside each image of a ragged batch; the others are never assigned.  That equals `assign` on the image's filtered
+        points while every level keeps a valid point in every image (the gts' levels are clamped to the levels present).
+        -> list of AssignResult, or None when the kernels do not take the inputs (the caller then assigns image by image)."""
         centroid = self.iou_type == 'centroid'
         if points.shape[0] == 0 or sum(g.shape[0] for g in gt_bboxes) == 0 or not _native(points, *gt_bboxes) or \
-                (centroid and not _native(*gt_extreme_pts)):
+                (centroid and not _native(*gt_extreme_pts)) or (valid is not None and not valid.is_cuda):
             return None
         from ..ops.backend import get_backend
         centres = None
@@ -175,7 +181,7 @@ class CentroidAssigner:
                        for g, e in zip(gt_bboxes, gt_extreme_pts)]
         lab = _long_labels(gt_labels)
         gt_inds, labels = get_backend(points).centroid_assign_batch(points[:, :3], [g[:, :4] for g in gt_bboxes], centres,
-                                                                    float(self.scale), self.pos_num, lab)
+                                                                    float(self.scale), self.pos_num, lab, valid=valid)
         return [AssignResult(g.shape[0], gt_inds[i], None,
                              labels=labels[i] if lab is not None else
                              _labels_of(gt_inds[i], None if gt_labels is None else gt_labels[i]))
@@ -328,16 +334,23 @@ class ATSSAssigner:
         return type(self.iou_calculator) is BboxOverlaps2D and 1 <= len(num_level_bboxes) <= 8 and \
             all(n >= self.topk for n in num_level_bboxes) and sum(num_level_bboxes) == num_bboxes
 
-    def assign_batch(self, bboxes, num_level_bboxes, gt_bboxes, gt_labels=None):
+    def assign_batch(self, bboxes, num_level_bboxes, gt_bboxes, gt_labels=None, valid=None, valid_counts=None):
         """bboxes (B, N, >= 4): the boxes of all images, the same levels in each; gt_bboxes / gt_labels: per-image lists (an
-        image may have no gt).  -> list of AssignResult, or None when the kernels do not take the inputs."""
+        image may have no gt).  valid: (B, N) bool / uint8 on the device or None -- the boxes that lie inside each image of a
+        ragged batch -- with valid_counts, per image the HOST count of valid boxes on every level (no device read is made
+        for them).  -> list of AssignResult as `assign` gives them on the image's filtered boxes, scattered back; or None
+        when the kernels do not take the inputs, a level with fewer than `topk` valid boxes among them: the caller then
+        assigns image by image and torch.topk's error on that level stays the observable behaviour."""
+        if valid is not None and (valid_counts is None or any(n < self.topk for counts in valid_counts for n in counts)):
+            return None
         if bboxes.shape[1] == 0 or sum(g.shape[0] for g in gt_bboxes) == 0 or not _native(bboxes, *gt_bboxes) or \
-                not self._native_levels(num_level_bboxes, bboxes.shape[1]):
+                not self._native_levels(num_level_bboxes, bboxes.shape[1]) or (valid is not None and not valid.is_cuda):
             return None
         from ..ops.backend import get_backend
         lab = _long_labels(gt_labels)
         gt_inds, max_overlaps, labels = get_backend(bboxes).atss_assign_batch(bboxes[..., :4], num_level_bboxes,
-                                                                              [g[:, :4] for g in gt_bboxes], self.topk, lab)
+                                                                              [g[:, :4] for g in gt_bboxes], self.topk, lab,
+                                                                              valid=valid, valid_counts=valid_counts)
         out = []
         for i, g in enumerate(gt_bboxes):
             if g.shape[0] == 0:     # (as `assign` answers an image without gts: overlaps 0, not -INF)

@@ -100,8 +100,10 @@ __global__ __launch_bounds__(1024) void centroid_prep_kernel(const float *__rest
     }
 }
 
-// one workgroup per gt: its pos_num nearest points of its level claim their words
-__global__ __launch_bounds__(1024) void centroid_claim_kernel(const float *__restrict__ points, int P, const float *__restrict__ gt,
+// one workgroup per gt: its pos_num nearest points of its level claim their words.  valid: (B, P) or NULL; a point that does
+// not exist for the gt's image is no candidate (the byte is read where the key is made: once for the rows cached in LDS)
+__global__ __launch_bounds__(1024) void centroid_claim_kernel(const float *__restrict__ points, int P,
+                                                              const uint8_t *__restrict__ valid, const float *__restrict__ gt,
                                                               const float *__restrict__ centres, AssignBatch bt, float scale,
                                                               int pos_num, const int *__restrict__ hdr, const int *__restrict__ lvl,
                                                               unsigned long long *__restrict__ word, int cap)
@@ -116,10 +118,11 @@ __global__ __launch_bounds__(1024) void centroid_claim_kernel(const float *__res
     const int gl = assign_gt_level(w, h, scale, hdr[0], hdr[1]);
     unsigned long long *wd = word + (size_t)b * P;
     const unsigned gi = (unsigned)(g - bt.off[b]);
+    const uint8_t *vb = valid ? valid + (size_t)b * P : nullptr;
     assign_select(
         P, P < cap ? P : cap, keys, red, pos_num,
         [&](int i) {
-            if (lvl[i] != gl) return ASSIGN_SKIP;
+            if (lvl[i] != gl || !assign_row_valid(vb, i)) return ASSIGN_SKIP;
             return assign_key(assign_centroid_distance(points[(size_t)i * 3], points[(size_t)i * 3 + 1], cx, cy, w, h));
         },
         [&](int, int row, unsigned key) { atomicMin(wd + row, ((unsigned long long)key << 32) | gi); });
@@ -132,9 +135,11 @@ struct AtssLevels {
 
 // workspace: u64 word[B * N] | int cand_row[G * nlev * k] | float cand_iou[G * nlev * k]
 // one workgroup per (gt, level): the level's topk boxes with the nearest centres -> the gt's candidate list; all workgroups
-// together clear the words
+// together clear the words.  valid: (B, N) or NULL; a row that does not exist for the gt's image is no candidate, a level
+// with fewer than topk existing rows fills fewer
 __global__ __launch_bounds__(1024) void atss_candidates_kernel(const float *__restrict__ boxes, int ld, int N, AtssLevels lv,
-                                                               const float *__restrict__ gt, AssignBatch bt, int topk,
+                                                               const uint8_t *__restrict__ valid, const float *__restrict__ gt,
+                                                               AssignBatch bt, int topk,
                                                                unsigned long long *__restrict__ word, int *__restrict__ cand_row,
                                                                float *__restrict__ cand_iou, int cap)
 {
@@ -147,11 +152,13 @@ __global__ __launch_bounds__(1024) void atss_candidates_kernel(const float *__re
     const float gx = assign_box_centre(box[0], box[2]), gy = assign_box_centre(box[1], box[3]);
     const int start = lv.start[sg], n = lv.len[sg];
     const float *seg = boxes + ((size_t)b * N + start) * ld;
+    const uint8_t *vseg = valid ? valid + (size_t)b * N + start : nullptr;
     const size_t slot = ((size_t)g * lv.n + sg) * topk;
-    for (int r = tid; r < topk; r += 1024) cand_row[slot + r] = -1;      // (a level with NaN distances fills fewer)
+    for (int r = tid; r < topk; r += 1024) cand_row[slot + r] = -1;      // (a level with NaN distances or masked rows fills fewer)
     assign_select(
         n, n < cap ? n : cap, keys, red, topk,
         [&](int i) {
+            if (!assign_row_valid(vseg, i)) return ASSIGN_SKIP;
             const float *q = seg + (size_t)i * ld;
             return assign_key(assign_centre_distance(assign_box_centre(q[0], q[2]), assign_box_centre(q[1], q[3]), gx, gy));
         },
@@ -173,7 +180,7 @@ __global__ __launch_bounds__(64) void atss_positive_kernel(const float *__restri
     const int *rows = cand_row + (size_t)g * ncand;
     float *iou = cand_iou + (size_t)g * ncand;
     int n = 0;
-    for (int i = 0; i < ncand; ++i)           // close the gaps a short candidate list leaves (NaN distances only)
+    for (int i = 0; i < ncand; ++i)           // close the gaps a short candidate list leaves (NaN distances, masked rows)
         if (rows[i] >= 0) iou[n++] = iou[i];
     const float thr = assign_atss_threshold(iou, n);
     const float *box = gt + (size_t)g * 4;
@@ -213,6 +220,49 @@ __global__ __launch_bounds__(256) void dense_targets_kernel(const int64_t *__res
         const size_t p = e / D;
         const int64_t g = gt_inds[p];
         out[e] = g > 0 ? table[(size_t)(g - 1) * D + (e - p * D)] : 0.f;
+    }
+}
+
+// The per-point targets of a stage for all images (assign_rows.h: assign_target_*): every workgroup walks the (B, P, D) rows and
+// then the points; workgroup b < B first counts image b's positives -- an integer sum of a fixed tree, no atomic.
+__global__ __launch_bounds__(256) void assign_targets_kernel(const int64_t *__restrict__ gt_inds, const uint8_t *__restrict__ valid,
+                                                             int P, AssignBatch bt, const float *__restrict__ table, int D,
+                                                             const int64_t *__restrict__ gt_labels, int64_t background,
+                                                             float *__restrict__ rows, int64_t *__restrict__ labels,
+                                                             float *__restrict__ label_weights, float *__restrict__ bbox_weights,
+                                                             int64_t *__restrict__ num_pos)
+{
+    __shared__ int red[4];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < bt.B) {
+        const int b = blockIdx.x, ng = bt.off[b + 1] - bt.off[b];
+        int n = 0;
+        for (int i = tid; i < P; i += 256) {
+            const size_t p = (size_t)b * P + i;
+            n += assign_target_positive(gt_inds[p], assign_row_valid(valid, p), ng);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+        if ((tid & 63) == 0) red[tid >> 6] = n;
+        __syncthreads();
+        if (tid == 0) num_pos[b] = (int64_t)(red[0] + red[1] + red[2] + red[3]);
+    }
+    const size_t npts = (size_t)bt.B * P, total = npts * D, step = (size_t)gridDim.x * 256;
+    for (size_t e = blockIdx.x * (size_t)256 + tid; e < total; e += step) {
+        const size_t p = e / D;
+        const int b = (int)(p / P), d = (int)(e - p * D);
+        const int64_t g = gt_inds[p];
+        const int pos = assign_target_positive(g, assign_row_valid(valid, p), bt.off[b + 1] - bt.off[b]);
+        rows[e] = assign_target_value(pos, table + (size_t)bt.off[b] * D, D, g, d);
+    }
+    for (size_t p = blockIdx.x * (size_t)256 + tid; p < npts; p += step) {
+        const int b = (int)(p / P);
+        const int64_t g = gt_inds[p];
+        const int ok = assign_row_valid(valid, p), pos = assign_target_positive(g, ok, bt.off[b + 1] - bt.off[b]);
+        labels[p] = assign_target_label(pos, ok, gt_labels ? gt_labels + bt.off[b] : nullptr, g, background);
+        label_weights[p] = assign_target_label_weight(ok);
+        const float w = assign_target_bbox_weight(pos);
+        reinterpret_cast<float4 *>(bbox_weights)[p] = make_float4(w, w, w, w);
     }
 }
 
@@ -257,9 +307,9 @@ int64_t lsn_assign_workspace_bytes(int P, int G, int nlev, int k)
     return 64 + (int64_t)P * 12 + cand * 8;       // header + levels + words, candidate rows + IoUs
 }
 
-int lsn_centroid_assign_batch(const float *points, int P, const float *gt_bboxes, const float *centres, int B,
-                              const int *gt_offset, float scale, int pos_num, const int64_t *gt_labels, int64_t *gt_inds,
-                              int64_t *labels, void *workspace, lsn_stream_t stream)
+int lsn_centroid_assign_masked_batch(const float *points, int P, const uint8_t *valid, const float *gt_bboxes, const float *centres,
+                                     int B, const int *gt_offset, float scale, int pos_num, const int64_t *gt_labels,
+                                     int64_t *gt_inds, int64_t *labels, void *workspace, lsn_stream_t stream)
 {
     AssignBatch bt;
     if (int rc = make_batch(bt, B, gt_offset, "centroid assign")) return rc;
@@ -275,12 +325,20 @@ int lsn_centroid_assign_batch(const float *points, int P, const float *gt_bboxes
     const int cap = select_lds_cap(reinterpret_cast<const void *>(centroid_claim_kernel), P);
     if (cap < 0) return cap;
     hipLaunchKernelGGL(centroid_prep_kernel, dim3(B), dim3(1024), 0, stream, points, P, hdr, lvl, word);
-    hipLaunchKernelGGL(centroid_claim_kernel, dim3(G), dim3(1024), (size_t)cap * 4, stream, points, P, gt_bboxes, centres, bt,
-                       scale, pos_num, hdr, lvl, word, cap);
+    hipLaunchKernelGGL(centroid_claim_kernel, dim3(G), dim3(1024), (size_t)cap * 4, stream, points, P, valid, gt_bboxes, centres,
+                       bt, scale, pos_num, hdr, lvl, word, cap);
     hipLaunchKernelGGL(assign_resolve_kernel<false>, dim3(resolve_blocks((size_t)B * P)), dim3(256), 0, stream, word, P, bt,
                        gt_labels, gt_inds, labels, static_cast<float *>(nullptr));
     LSN_HIP(hipGetLastError());
     return 0;
+}
+
+int lsn_centroid_assign_batch(const float *points, int P, const float *gt_bboxes, const float *centres, int B,
+                              const int *gt_offset, float scale, int pos_num, const int64_t *gt_labels, int64_t *gt_inds,
+                              int64_t *labels, void *workspace, lsn_stream_t stream)
+{
+    return lsn_centroid_assign_masked_batch(points, P, nullptr, gt_bboxes, centres, B, gt_offset, scale, pos_num, gt_labels,
+                                            gt_inds, labels, workspace, stream);
 }
 
 int lsn_centroid_assign(const float *points, int P, const float *gt_bboxes, const float *centres, int G, float scale,
@@ -292,9 +350,9 @@ int lsn_centroid_assign(const float *points, int P, const float *gt_bboxes, cons
                                      workspace, stream);
 }
 
-int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int B,
-                          const int *gt_offset, int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps,
-                          int64_t *labels, void *workspace, lsn_stream_t stream)
+int lsn_atss_assign_masked_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len, const uint8_t *valid,
+                                 const float *gt_bboxes, int B, const int *gt_offset, int topk, const int64_t *gt_labels,
+                                 int64_t *gt_inds, float *max_overlaps, int64_t *labels, void *workspace, lsn_stream_t stream)
 {
     AssignBatch bt;
     if (int rc = make_batch(bt, B, gt_offset, "atss assign")) return rc;
@@ -322,14 +380,22 @@ int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const in
     float *cand_iou = reinterpret_cast<float *>(cand_row + ncand);
     const int cap = select_lds_cap(reinterpret_cast<const void *>(atss_candidates_kernel), nmax);
     if (cap < 0) return cap;
-    hipLaunchKernelGGL(atss_candidates_kernel, dim3(G, nlev), dim3(1024), (size_t)cap * 4, stream, bboxes, ld, N, lv, gt_bboxes,
-                       bt, topk, word, cand_row, cand_iou, cap);
+    hipLaunchKernelGGL(atss_candidates_kernel, dim3(G, nlev), dim3(1024), (size_t)cap * 4, stream, bboxes, ld, N, lv, valid,
+                       gt_bboxes, bt, topk, word, cand_row, cand_iou, cap);
     hipLaunchKernelGGL(atss_positive_kernel, dim3(cdiv(G, 64)), dim3(64), 0, stream, bboxes, ld, N, nlev * topk, gt_bboxes, bt, G,
                        word, cand_row, cand_iou);
     hipLaunchKernelGGL(assign_resolve_kernel<true>, dim3(resolve_blocks((size_t)B * N)), dim3(256), 0, stream, word, N, bt,
                        gt_labels, gt_inds, labels, max_overlaps);
     LSN_HIP(hipGetLastError());
     return 0;
+}
+
+int lsn_atss_assign_batch(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int B,
+                          const int *gt_offset, int topk, const int64_t *gt_labels, int64_t *gt_inds, float *max_overlaps,
+                          int64_t *labels, void *workspace, lsn_stream_t stream)
+{
+    return lsn_atss_assign_masked_batch(bboxes, ld, N, nlev, level_len, nullptr, gt_bboxes, B, gt_offset, topk, gt_labels, gt_inds,
+                                        max_overlaps, labels, workspace, stream);
 }
 
 int lsn_atss_assign(const float *bboxes, int ld, int N, int nlev, const int *level_len, const float *gt_bboxes, int G,
@@ -348,6 +414,24 @@ int lsn_dense_targets(const int64_t *gt_inds, int P, const float *table, int D, 
     LSN_CHECK(gt_inds && table && out, "dense targets: NULL argument");
     const size_t total = (size_t)P * D;
     hipLaunchKernelGGL(dense_targets_kernel, dim3(resolve_blocks(total) * 2), dim3(256), 0, stream, gt_inds, total, D, table, out);
+    LSN_HIP(hipGetLastError());
+    return 0;
+}
+
+int lsn_assign_targets_batch(const int64_t *gt_inds, const uint8_t *valid, int P, int B, const int *gt_offset, const float *table,
+                             int D, const int64_t *gt_labels, int64_t background_label, float *rows, int64_t *labels,
+                             float *label_weights, float *bbox_weights, int64_t *num_pos, lsn_stream_t stream)
+{
+    AssignBatch bt;
+    if (int rc = make_batch(bt, B, gt_offset, "assign targets")) return rc;
+    LSN_CHECK(P > 0 && D > 0, "assign targets: P = %d, D = %d", P, D);
+    LSN_CHECK(gt_inds && rows && labels && label_weights && bbox_weights && num_pos, "assign targets: NULL argument");
+    LSN_CHECK(table || bt.off[B] == 0, "assign targets: %d gts without a table", bt.off[B]);
+    LSN_CHECK((long long)B * P < (1ll << 31), "assign targets: %d x %d points", B, P);
+    LSN_CHECK((reinterpret_cast<uintptr_t>(bbox_weights) & 15) == 0, "assign targets: bbox_weights must be 16-byte aligned");
+    const int want = resolve_blocks((size_t)B * P * D) * 2;
+    hipLaunchKernelGGL(assign_targets_kernel, dim3(want > B ? want : B), dim3(256), 0, stream, gt_inds, valid, P, bt, table, D,
+                       gt_labels, background_label, rows, labels, label_weights, bbox_weights, num_pos);
     LSN_HIP(hipGetLastError());
     return 0;
 }

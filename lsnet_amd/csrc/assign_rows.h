@@ -12,6 +12,7 @@
 // flip, and the strides are powers of two.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -44,6 +45,31 @@ LSN_HD float assign_key_value(uint32_t key)
     union { float f; uint32_t u; } c;
     c.u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
     return c.f;
+}
+
+// ---- ragged batches ----------------------------------------------------------------------------------------------
+// Row i exists for the image whose mask row is `valid` (NULL: every row exists) -- the `inside` flags of a batch padded
+// to its largest image.  A row that does not exist is never a candidate of that image's gts.
+LSN_HD int assign_row_valid(const uint8_t *valid, size_t i) { return valid == 0 || valid[i] != 0; }
+
+// The per-point targets LSHead builds from an assignment (lsnet_head.py:834-917: the targets of the filtered points,
+// unmapped into the full grid with zeros).  gt_ind: 1-based gt of the image, num_gts: how many the image has.
+LSN_HD int assign_target_positive(int64_t gt_ind, int valid, int num_gts) { return valid && gt_ind > 0 && gt_ind <= num_gts; }
+
+// label of a point: its gt's label (1 without gt_labels), the background label where nothing was assigned, 0 outside the image
+LSN_HD int64_t assign_target_label(int positive, int valid, const int64_t *image_gt_labels, int64_t gt_ind, int64_t background)
+{
+    if (!valid) return 0;
+    if (!positive) return background;
+    return image_gt_labels ? image_gt_labels[gt_ind - 1] : 1;
+}
+
+LSN_HD float assign_target_label_weight(int valid) { return valid ? 1.f : 0.f; }
+LSN_HD float assign_target_bbox_weight(int positive) { return positive ? 1.f : 0.f; }
+// column d of the point's target row: its gt's table row, zeros otherwise
+LSN_HD float assign_target_value(int positive, const float *image_table, int D, int64_t gt_ind, int d)
+{
+    return positive ? image_table[(size_t)(gt_ind - 1) * D + d] : 0.f;
 }
 
 // ---- Centroid assigner -------------------------------------------------------------------------------------------

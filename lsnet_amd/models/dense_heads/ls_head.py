@@ -495,23 +495,36 @@ class LSHead(nn.Module):
                str(device))
         hit = self._consts.get(key)
         if hit is not None:
-            return hit
+            return hit[:3]
         points = [self.point_generators[i].grid_points(featmap_sizes[i], self.point_strides[i], device)
                   for i in range(len(featmap_sizes))]
-        flags, all_valid = [], True
+        flags, counts, all_valid = [], [], True
         for meta in img_metas:
-            per_level = []
+            per_level, per_count = [], []
             h, w = meta['pad_shape'][:2]
             for i, (fh, fw) in enumerate(featmap_sizes):
                 s = self.point_strides[i]
                 vh, vw = min(int(np.ceil(h / s)), fh), min(int(np.ceil(w / s)), fw)
                 all_valid = all_valid and vh == fh and vw == fw
                 per_level.append(self.point_generators[i].valid_flags((fh, fw), (vh, vw), device))
+                per_count.append(vh * vw)
             flags.append(per_level)
+            counts.append(per_count)
         if len(self._consts) > 64:            # multi-scale training visits many geometries: keep the table small
             self._consts.clear()
-        self._consts[key] = (points, flags, all_valid)
+        # beside them, for the batched assignment of a ragged batch: the flags as one (B, P) mask and, as host integers,
+        # how many cells of every level each image keeps
+        mask = torch.stack([torch.cat(f) for f in flags]) if flags and flags[0] else None
+        self._consts[key] = (points, flags, all_valid, mask, counts)
         return points, flags, all_valid
+
+    def get_valid(self, featmap_sizes, img_metas, device):
+        """-> ((B, P) bool mask, per image the per-level counts of valid cells as Python ints): `get_points`' flags in the form
+        the batched assignment takes, cached with them under the same key."""
+        self.get_points(featmap_sizes, img_metas, device)
+        key = ('points', tuple(tuple(s) for s in featmap_sizes), tuple(tuple(m['pad_shape'][:2]) for m in img_metas),
+               str(device))
+        return self._consts[key][3:]
 
     def _dense_targets(self, gt_inds, gt_labels, gt_bboxes, extra):
         """Per-point targets from an assignment WITHOUT index lists: positives are rows with
@@ -549,6 +562,9 @@ class LSHead(nn.Module):
                        label_weights=proposals.new_ones((n_all,)), num_pos=proposals.new_zeros((), dtype=torch.long))
             for k, v in extra.items():
                 out[k] = zeros((n_all, v.shape[1]))
+            if not all_valid:         # as the scatter below leaves them (lsnet_head.py:893-896): outside cells label 0, weight 0
+                out['labels'] = torch.where(flags, self.background_label, 0)
+                out['label_weights'] = flags.to(proposals.dtype)
             return out
         inside = None if all_valid else flags
         props = proposals if inside is None else proposals[inside]
@@ -573,10 +589,11 @@ class LSHead(nn.Module):
             out = full
         return out
 
-    def _assign_batch(self, stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list):
-        """The stage's assignment of ALL images in one call of the library (every grid cell valid, so the images share points
-        and levels) -> per-image AssignResults, or None: the assigner has no batched form or its kernels do not take these
-        inputs, and the images are assigned one by one."""
+    def _assign_batch(self, stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list, valid=None, valid_counts=None):
+        """The stage's assignment of ALL images in one call of the library (the images share points and levels; `valid`: the
+        (B, P) mask of the cells inside each image when not every cell is, `valid_counts` their per-level counts on the host)
+        -> per-image AssignResults, or None: the assigner has no batched form or its kernels do not take these inputs, and the
+        images are assigned one by one."""
         assigner = self.init_assigner if stage == 'init' else self.refine_assigner
         fn = getattr(assigner, 'assign_batch', None)
         if fn is None:
@@ -585,16 +602,52 @@ class LSHead(nn.Module):
             points = proposals_list[0]
             if any(p is not points for p in proposals_list):
                 return None
-            return fn(points, list(gt_bboxes_list), [e.get('extremes_gt') for e in extra_list])
+            kw = {} if valid is None else dict(valid=valid)
+            return fn(points, list(gt_bboxes_list), [e.get('extremes_gt') for e in extra_list], **kw)
         if stacked is None:
             return None
-        return fn(stacked, num_level, list(gt_bboxes_list))
+        kw = {} if valid is None else dict(valid=valid, valid_counts=valid_counts)
+        return fn(stacked, num_level, list(gt_bboxes_list), **kw)
+
+    def _ragged_targets(self, proposals_list, num_level, gt_bboxes_list, gt_labels_list, extra_list, stage, stacked, valid,
+                        valid_counts):
+        """`get_targets` for a batch in which not every grid cell lies inside every image, without visiting the images: one
+        masked assignment call and one target call of the library (lsn_*_assign_masked_batch, lsn_assign_targets_batch) --
+        the values the per-image path leaves after filtering the points, assigning, gathering and scattering back, with no
+        boolean index and no host read.  -> (targets, positive count), or None where the kernels do not take the inputs."""
+        if not (assigners.NATIVE_RAGGED and assigners.NATIVE_ASSIGN) or valid is None or valid_counts is None:
+            return None
+        keys = list(extra_list[0])
+        fields = [[g] + [e[k] for k in keys] for g, e in zip(gt_bboxes_list, extra_list)]
+        if any(list(e) != keys for e in extra_list) or \
+                not all(v.is_cuda and v.dtype == torch.float32 and v.dim() == 2 for f in fields for v in f) or \
+                not all(g.shape[1] == 4 for g in gt_bboxes_list) or \
+                (gt_labels_list is not None and any(l is None or l.dtype != torch.long for l in gt_labels_list)):
+            return None
+        results = self._assign_batch(stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list, valid, valid_counts)
+        if results is None:
+            return None
+        gt_inds = torch.stack([r.gt_inds for r in results])
+        tables = [f[0] if len(f) == 1 else torch.cat(f, dim=1) for f in fields]
+        rows, labels, label_weights, bbox_weights, num_pos = get_backend(gt_inds).assign_targets_batch(
+            gt_inds, valid, tables, gt_labels_list, self.background_label)
+        widths = [v.shape[1] for v in fields[0]]
+        parts = torch.split(rows, widths, dim=2)
+        out = dict(bboxes_gt=parts[0], bbox_weights=bbox_weights, labels=labels, label_weights=label_weights)
+        out.update(zip(keys, parts[1:]))
+        return out, num_pos.clamp(min=1).sum()
 
     def get_targets(self, proposals_list, flags_list, all_valid, num_level, gt_bboxes_list, gt_labels_list,
-                    extra_list, stage, stacked=None):
+                    extra_list, stage, stacked=None, valid=None, valid_counts=None):
         """All images of the batch -> per-level target tensors (B, N_l, ...) plus the positive count
         sum_img max(n_pos, 1) as a DEVICE scalar (lsnet_head.py:919-1019).  `stacked`: the (B, N, 4) tensor whose rows
-        `proposals_list` holds, when there is one."""
+        `proposals_list` holds, when there is one.  `valid` / `valid_counts`: `get_valid`'s, for a batch that is not all_valid
+        (without them, or with LSNET_NATIVE_RAGGED=0, such a batch is assigned image by image)."""
+        if not all_valid:
+            ragged = self._ragged_targets(proposals_list, num_level, gt_bboxes_list, gt_labels_list, extra_list, stage, stacked,
+                                          valid, valid_counts)
+            if ragged is not None:
+                return ragged
         results = self._assign_batch(stage, proposals_list, stacked, num_level, gt_bboxes_list, extra_list) if all_valid else None
         per_img = [self._assign_image(stage, proposals_list[i], flags_list[i], all_valid, num_level,
                                       gt_bboxes_list[i], None if gt_labels_list is None else gt_labels_list[i],
@@ -761,11 +814,12 @@ class LSHead(nn.Module):
         num_level = [p.shape[0] for p in points]
         flat_points = torch.cat(points)
         flat_flags = [torch.cat(f) for f in flags]
+        valid, valid_counts = (None, None) if all_valid else self.get_valid(featmap_sizes, img_metas, device)
         tg_init, n_init = self.get_targets([flat_points] * num_imgs, flat_flags, all_valid, num_level, gt_bboxes,
-                                           gt_labels, extra, 'init')
+                                           gt_labels, extra, 'init', valid=valid, valid_counts=valid_counts)
         return dict(featmap_sizes=featmap_sizes, extra=extra, gt_bboxes=gt_bboxes, gt_labels=gt_labels, points=points,
                     flat_points=flat_points, all_valid=all_valid, num_level=num_level, flat_flags=flat_flags, tg_init=tg_init,
-                    n_init=n_init)
+                    n_init=n_init, valid=valid, valid_counts=valid_counts)
 
     def _box_branch(self):
         return 'bbox' if 'bbox' in self.branches else self.branches[0]
@@ -792,7 +846,7 @@ class LSHead(nn.Module):
             boxes = torch.cat(decoded, dim=1)
         return self.get_targets([boxes[i] for i in range(num_imgs)], init_stage['flat_flags'], init_stage['all_valid'],
                                 init_stage['num_level'], init_stage['gt_bboxes'], init_stage['gt_labels'], init_stage['extra'],
-                                'refine', stacked=boxes)
+                                'refine', stacked=boxes, valid=init_stage.get('valid'), valid_counts=init_stage.get('valid_counts'))
 
     def loss(self, cls_scores, bbox_pts_preds_init, bbox_pts_preds_refine, segm_pts_preds_init,
              segm_pts_preds_refine, pose_pts_preds_init, pose_pts_preds_refine, gt_bboxes, gt_extremes,

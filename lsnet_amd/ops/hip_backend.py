@@ -590,9 +590,11 @@ class HipBackend:
             rows = _f32(rows, what)
         return rows.contiguous(), (ctypes.c_int * len(offs))(*offs), offs[-1]
 
-    def centroid_assign_batch(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, out=None):
+    def centroid_assign_batch(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, valid=None, out=None):
         """points (P, 3) shared by the B images; gt_bboxes / centres / gt_labels: lists of B per-image tensors ((G_b, 4),
         (G_b, 2) or None for the box centres, (G_b,) int64 or None).  -> (gt_inds (B, P) int64, labels (B, P) or None).
+        `valid`: (B, P) bool / uint8 or None -- the points that exist for each image of a ragged batch; the others are nobody's
+        candidates and come out as background (lsn_centroid_assign_masked_batch).
         `out`: preallocated (gt_inds, labels, workspace) for callers that must not allocate (graph capture)."""
         lib = _lib.load()
         points = _f32(points, 'points').contiguous()
@@ -610,21 +612,39 @@ class HipBackend:
         else:
             gt_inds, labels, ws = out
             assert ws.numel() >= nbytes and gt_inds.numel() == B * P and gt_inds.is_contiguous()
-        _lib.check(lib.lsn_centroid_assign_batch(ptr(points), P, ptr(gts), ptr(cen), B, offs, scale, int(pos_num),
-                                                 ptr(lab), ptr(gt_inds), ptr(labels), ptr(ws), stream()))
+        if valid is None:
+            _lib.check(lib.lsn_centroid_assign_batch(ptr(points), P, ptr(gts), ptr(cen), B, offs, scale, int(pos_num),
+                                                     ptr(lab), ptr(gt_inds), ptr(labels), ptr(ws), stream()))
+        else:
+            valid = self._u8(valid, (B, P), points.device)
+            _lib.check(lib.lsn_centroid_assign_masked_batch(ptr(points), P, ptr(valid), ptr(gts), ptr(cen), B, offs, scale,
+                                                            int(pos_num), ptr(lab), ptr(gt_inds), ptr(labels), ptr(ws),
+                                                            stream()))
         return gt_inds, labels
 
     def centroid_assign(self, points, gt_bboxes, centres, scale, pos_num, gt_labels=None, out=None):
         """One image: -> (gt_inds (P,), labels (P,) or None); see centroid_assign_batch."""
         gt_inds, labels = self.centroid_assign_batch(points, [gt_bboxes], None if centres is None else [centres], scale,
-                                                     pos_num, None if gt_labels is None else [gt_labels], out)
+                                                     pos_num, None if gt_labels is None else [gt_labels], out=out)
         return gt_inds.view(-1), None if labels is None else labels.view(-1)
 
-    def atss_assign_batch(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, out=None):
+    def atss_assign_batch(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, valid=None, valid_counts=None, out=None):
         """bboxes (B, N, >= 4) float32; level_len: the levels' box counts (sum = N, shared by the images); gt_bboxes /
         gt_labels: lists of B per-image tensors.  -> (gt_inds (B, N), max_overlaps (B, N), labels (B, N) or None).
+        `valid`: (B, N) bool / uint8 or None -- the boxes that exist for each image of a ragged batch
+        (lsn_atss_assign_masked_batch); `valid_counts`: with it, B lists of HOST ints, the valid boxes per level.  The kernels
+        answer a level with fewer than `topk` valid boxes with a shorter candidate list where torch.topk raises: such a
+        count is refused here (NotImplementedError), so that the caller's torch path keeps that error.
         `out`: preallocated (gt_inds, max_overlaps, labels, workspace)."""
         lib = _lib.load()
+        if valid is not None:
+            if valid_counts is None or len(valid_counts) != bboxes.shape[0] or \
+                    any(len(c) != len(level_len) for c in valid_counts):
+                raise ValueError('atss_assign_batch: a mask needs valid_counts, per image one host integer per level')
+            short = [(b, l, int(n)) for b, c in enumerate(valid_counts) for l, n in enumerate(c) if int(n) < int(topk)]
+            if short:
+                raise NotImplementedError(f'atss_assign_batch: image {short[0][0]} has {short[0][2]} valid boxes on level '
+                                          f'{short[0][1]}, topk = {int(topk)}')
         bboxes = _f32(bboxes, 'bboxes')
         if bboxes.stride(2) != 1 or bboxes.stride(1) < bboxes.shape[2] or \
                 (bboxes.shape[0] > 1 and bboxes.stride(0) != bboxes.shape[1] * bboxes.stride(1)):
@@ -646,14 +666,20 @@ class HipBackend:
         else:
             gt_inds, overlaps, labels, ws = out
             assert ws.numel() >= nbytes and gt_inds.numel() == B * N and gt_inds.is_contiguous() and overlaps.is_contiguous()
-        _lib.check(lib.lsn_atss_assign_batch(ptr(bboxes), bboxes.stride(1), N, nlev, lens, ptr(gts), B, offs, int(topk),
-                                             ptr(lab), ptr(gt_inds), ptr(overlaps), ptr(labels), ptr(ws), stream()))
+        if valid is None:
+            _lib.check(lib.lsn_atss_assign_batch(ptr(bboxes), bboxes.stride(1), N, nlev, lens, ptr(gts), B, offs, int(topk),
+                                                 ptr(lab), ptr(gt_inds), ptr(overlaps), ptr(labels), ptr(ws), stream()))
+        else:
+            valid = self._u8(valid, (B, N), bboxes.device)
+            _lib.check(lib.lsn_atss_assign_masked_batch(ptr(bboxes), bboxes.stride(1), N, nlev, lens, ptr(valid), ptr(gts), B,
+                                                        offs, int(topk), ptr(lab), ptr(gt_inds), ptr(overlaps), ptr(labels),
+                                                        ptr(ws), stream()))
         return gt_inds, overlaps, labels
 
     def atss_assign(self, bboxes, level_len, gt_bboxes, topk, gt_labels=None, out=None):
         """One image, bboxes (N, >= 4): -> (gt_inds (N,), max_overlaps (N,), labels (N,) or None)."""
         gt_inds, overlaps, labels = self.atss_assign_batch(bboxes[None], level_len, [gt_bboxes], topk,
-                                                           None if gt_labels is None else [gt_labels], out)
+                                                           None if gt_labels is None else [gt_labels], out=out)
         return gt_inds.view(-1), overlaps.view(-1), None if labels is None else labels.view(-1)
 
     def dense_targets(self, gt_inds, table):
@@ -668,6 +694,41 @@ class HipBackend:
         out = torch.empty((P, D), dtype=torch.float32, device=table.device)
         _lib.check(lib.lsn_dense_targets(ptr(gt_inds), P, ptr(table), D, ptr(out), stream()))
         return out
+
+    def assign_targets_batch(self, gt_inds, valid, gt_tables, gt_labels, background_label, out=None):
+        """The per-point targets of a stage for all images in one launch (lsn_assign_targets_batch): gt_inds (B, P) int64;
+        valid (B, P) bool / uint8 or None; gt_tables: list of B per-image (G_b, D) float32 tables (boxes, then the other target
+        fields side by side), an image may have none; gt_labels: list of B (G_b,) int64 tensors or None.
+        -> rows (B, P, D), labels (B, P) int64, label_weights (B, P), bbox_weights (B, P, 4), num_pos (B,) int64.
+        `out`: these five, preallocated."""
+        lib = _lib.load()
+        gt_inds = gt_inds.contiguous()
+        if gt_inds.dtype != torch.int64 or gt_inds.dim() != 2 or gt_inds.shape[0] != len(gt_tables):
+            raise TypeError(f'gt_inds must be int64 (B, P) with one row per table, got {gt_inds.dtype} {tuple(gt_inds.shape)}')
+        B, P = gt_inds.shape
+        dev = gt_inds.device
+        table, offs, G = self._assign_gts(gt_tables, 'gt_tables')
+        D = table.shape[1]
+        lab = None if gt_labels is None else self._assign_gts(gt_labels, None)[0]
+        if lab is not None and (lab.dtype != torch.int64 or lab.numel() != G):
+            raise TypeError(f'gt_labels must be int64, one per table row; got {lab.dtype} x {lab.numel()} for {G} rows')
+        valid = self._u8(valid, (B, P), dev)
+        if out is None:
+            rows = torch.empty((B, P, D), dtype=torch.float32, device=dev)
+            labels = torch.empty((B, P), dtype=torch.int64, device=dev)
+            label_weights = torch.empty((B, P), dtype=torch.float32, device=dev)
+            bbox_weights = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+            num_pos = torch.empty((B,), dtype=torch.int64, device=dev)
+        else:
+            rows, labels, label_weights, bbox_weights, num_pos = out
+            assert rows.numel() == B * P * D and labels.numel() == B * P and label_weights.numel() == B * P
+            assert bbox_weights.numel() == B * P * 4 and num_pos.numel() == B
+            assert all(t.is_contiguous() for t in out) and labels.dtype == torch.int64 and num_pos.dtype == torch.int64
+            _f32(rows, 'rows'), _f32(label_weights, 'label_weights'), _f32(bbox_weights, 'bbox_weights')
+        _lib.check(lib.lsn_assign_targets_batch(ptr(gt_inds), ptr(valid), P, B, offs, ptr(table), D, ptr(lab),
+                                                int(background_label), ptr(rows), ptr(labels), ptr(label_weights),
+                                                ptr(bbox_weights), ptr(num_pos), stream()))
+        return rows, labels, label_weights, bbox_weights, num_pos
 
     # ------------------------------------------------------------------ LSHead's point decoding (csrc/points.hip)
     _point_tables = {}
