@@ -13,6 +13,7 @@
 //   weight gradient: a lane owns one (co, ci) pair of one group and the 9 taps; the block walks a range of pixels,
 //     every load of a wave falls into one or two cache lines (broadcast); partial sums meet in fp32 atomics.
 #include "common.h"
+#include "prof.h"
 
 namespace lsn {
 
@@ -146,6 +147,16 @@ __global__ __launch_bounds__(256) void gconv_wgrad_kernel(const GcArgs a)
     if (a.gb && ci == 0) atomic_add_f32(a.gb + g * CG + co, bsum);
 }
 
+// the launch log's entry of one pass (csrc/prof.h): every pass multiplies each (pixel, filter) by the 9 CG taps of its group once
+// and moves the input map, the output map and the weights
+struct GcProf : ProfSpan {
+    GcProf(const GcArgs &a, int Co, hipStream_t s)
+        : ProfSpan(PROF_GCONV, 2.0 * a.B * a.Ho * a.Wo * Co * a.kh * a.kw * (a.C / a.groups),
+                   4.0 * ((double)a.B * a.H * a.W * a.C + (double)a.B * a.Ho * a.Wo * Co + (double)Co * a.kh * a.kw * (a.C / a.groups)), s)
+    {
+    }
+};
+
 static int gc_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 static int gc_fill(GcArgs &a, int B, int H, int W, int C, int Co, int kh, int kw, int stride, int pad, int dil, int groups)
@@ -197,6 +208,7 @@ int lsn_grouped_conv2d_forward(const float *x, const float *w, const float *bias
     if (int rc = gc_fill(a, B, H, W, C, Co, kh, kw, stride, pad, dil, groups)) return rc;
     a.x = x, a.w = w, a.bias = bias, a.out = out, a.relu = relu;
     a.P = B * a.Ho * a.Wo;
+    GcProf prof(a, Co, static_cast<hipStream_t>(stream));
     return gc_launch<false>(a, static_cast<hipStream_t>(stream));
 }
 
@@ -209,6 +221,7 @@ int lsn_grouped_conv2d_backward_data(const float *grad_out, const float *w, floa
     if (int rc = gc_fill(a, B, H, W, C, Co, kh, kw, stride, pad, dil, groups)) return rc;
     a.gout = grad_out, a.w = w, a.out = grad_in;
     a.P = B * H * W;
+    GcProf prof(a, Co, static_cast<hipStream_t>(stream));
     return gc_launch<true>(a, static_cast<hipStream_t>(stream));
 }
 
@@ -223,6 +236,7 @@ int lsn_grouped_conv2d_backward_weight(const float *x, const float *grad_out, fl
     a.x = x, a.gout = grad_out, a.gw = grad_w, a.gb = grad_bias;
     a.P = B * a.Ho * a.Wo;
     const int cg = C / groups, K = kh * kw;
+    GcProf prof(a, Co, st);
     if (!accumulate) {
         LSN_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * (size_t)Co * K * cg, st));
         if (grad_bias) LSN_HIP(hipMemsetAsync(grad_bias, 0, sizeof(float) * (size_t)Co, st));
